@@ -7,6 +7,7 @@ of a synthetic scene whose geometry, layer table and styles are already resident
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME | --svg FILE [--svg-scale S]]
                     [--in-flight F] [--mode multi|exchange|bands|frames] [--no-animated] [--no-cpu-baseline]
+                    [--dump-outputs DIR]
 
 N = 1.  ONE renderer context — what a caller of `Renderer::render` has — renders exactly K frames; `value` = K / wall time.
 The context keeps `--in-flight` F frame slots (default 3, `forma_hip_set_frames_in_flight`): a device-resident frame is
@@ -90,8 +91,45 @@ def parse():
     ap.add_argument("--no-d2h", action="store_true", help="skip the PCIe-inclusive legs (profiling runs: their pipelined frames would be "
                     "averaged into the per-kernel durations of the one-frame-in-flight region)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the image the last timed step rendered to DIR/*.npy (float32 / float64, at most "
+                         "64 MB: the whole image when it fits, else a fixed seeded sample of its pixels; always its exact row sums)")
     ap.add_argument("--preflight", default=None, help=argparse.SUPPRESS)     # child process: try a multi-device context, print OK
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BUDGET = 64_000_000         # bytes of .npy data --dump-outputs may write
+DUMP_SAMPLE_PIXELS = 1 << 21      # pixels in the sample of an image too large to write whole (34 MB of RGBA + 17 MB of indices)
+DUMP_SAMPLE_SEED = 20240601
+
+
+def dump_outputs(out_dir, image, width, height):
+    """What the timed path computed in its last step — the RGBA8 image a caller reads back — as float .npy files in `out_dir`:
+      image_rgba.npy          float32 (H, W, 4), when it fits in the budget; otherwise
+      image_rgba_sample.npy   float32 (N, 4) the RGBA of N pixels drawn without replacement by a fixed seed, and
+      image_sample_pixel.npy  float64 (N,)   their flat indices y * W + x (ascending);
+      image_row_sums.npy      float64 (H, 4) the exact sum of every row's channels over the WHOLE image.
+    The same arguments render the same seeded scene, so two builds can be compared file for file.  Returns {file: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name in ("image_rgba.npy", "image_rgba_sample.npy", "image_sample_pixel.npy", "image_row_sums.npy"):
+        if os.path.exists(os.path.join(out_dir, name)):           # (no file of an earlier run with another canvas stays behind)
+            os.remove(os.path.join(out_dir, name))
+    px = np.ascontiguousarray(image).reshape(height, width, 4)
+    files = {"image_row_sums.npy": px.sum(axis=1, dtype=np.float64)}
+    if px.size * 4 + files["image_row_sums.npy"].nbytes <= DUMP_BUDGET:
+        files["image_rgba.npy"] = px.astype(np.float32)
+    else:
+        n = min(DUMP_SAMPLE_PIXELS, width * height)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(width * height, size=n, replace=False))
+        files["image_rgba_sample.npy"] = px.reshape(-1, 4)[idx].astype(np.float32)
+        files["image_sample_pixel.npy"] = idx.astype(np.float64)
+    assert sum(a.nbytes for a in files.values()) <= DUMP_BUDGET
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name), a)
+    return {name: list(a.shape) for name, a in files.items()}
 
 
 def preflight(devices):
@@ -275,6 +313,13 @@ def main():
         elapsed = timed(lambda: frames(args.steps))                 # THE timed region: exactly K frames -> `value`
         fps = frames_per_step * args.steps / elapsed
         ms_per_step = elapsed / args.steps * 1e3
+        # --dump-outputs: the image of the last timed frame, read back untimed (the file writing waits for the line's end)
+        last_image = None
+        if args.dump_outputs and primary and rank == 0 and driver:
+            if mode in ("single", "multi", "frames"):
+                last_image = ctx.read_image(width, height)
+            else:
+                print(f"bench.py --dump-outputs: --mode {mode} leaves one band of the image per rank; nothing written", file=sys.stderr)
         blocks = [rate(args.steps, frames_per_step) for _ in range(5)]
         # the multi-device context's two layouts (forma_hip_multi_layout): `value` is the default's (AUTO), both are listed
         layouts = None
@@ -544,6 +589,9 @@ def main():
             out["animated"] = animated_leg(local, args.animated_frames)
         if primary and rank == 0 and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(renderer, width, height, args.cpu_seconds)
+        if last_image is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "files": dump_outputs(args.dump_outputs, last_image, width, height),
+                                   "what": "the RGBA8 image of the last timed step as float (dump_outputs() in bench.py)"}
         if ctx is not None:
             try:
                 ctx.close()                                         # free the device buffers before the next workload
@@ -613,6 +661,8 @@ def main():
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.abspath(__file__), "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup",
                str(args.warmup), "--workload", args.workload, "--mode", "exchange"]
+        if args.dump_outputs:
+            cmd += ["--dump-outputs", args.dump_outputs]
         p = subprocess.run(cmd, capture_output=True, text=True)
         line = next((ln for ln in reversed(p.stdout.splitlines()) if ln.startswith("{")), None)
         if p.returncode != 0 or line is None:

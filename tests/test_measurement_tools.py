@@ -1,6 +1,6 @@
 """The measurement helpers the driver's bench run goes through, on CPU (no GPU, no rocprofv3 run): the counter tables of
 `tools/pmc_round.py` from rocprofv3's CSV, `bench.live_traffic` falling back without losing the line, and the issue classes
-`tools/isa_mix.py` prices a kernel's ISA with (profiles/r06_valu_issue_peak.txt)."""
+`tools/isa_mix.py` prices a kernel's ISA with (profiles/r06_valu_issue_peak.txt), and what `bench.py --dump-outputs` writes."""
 import importlib
 import os
 import subprocess
@@ -83,3 +83,34 @@ def test_isa_mix_prices_half_rate_instructions_double(tmp_path):
                  ".Lfunc_end0:\n")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "isa_mix.py"), str(s), "_Z3foo"], capture_output=True, text=True, check=True).stdout
     assert "VALU 8 = full 3 + half 4 + quarter 1 -> 15 full-rate slots" in out and "SALU 1, LDS 1, memory 1" in out
+
+
+def test_dump_outputs_writes_the_whole_image_or_a_fixed_sample_within_64_mb(tmp_path):
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(7)
+    small = rng.integers(0, 256, (108, 192 * 4), dtype=np.uint8)
+    files = bench.dump_outputs(str(tmp_path / "s"), small, 192, 108)
+    assert files == {"image_row_sums.npy": [108, 4], "image_rgba.npy": [108, 192, 4]}
+    img = np.load(tmp_path / "s" / "image_rgba.npy")
+    assert img.dtype == np.float32 and np.array_equal(img, small.reshape(108, 192, 4))
+    sums = np.load(tmp_path / "s" / "image_row_sums.npy")
+    assert sums.dtype == np.float64 and np.array_equal(sums, small.reshape(108, 192, 4).sum(axis=1))
+    # a 4K image does not fit whole: the same seeded pixels every time, their indices, and the exact row sums
+    big = rng.integers(0, 256, (2160, 3840 * 4), dtype=np.uint8)
+    for d in ("a", "b"):
+        assert bench.dump_outputs(str(tmp_path / d), big, 3840, 2160) == {
+            "image_row_sums.npy": [2160, 4], "image_rgba_sample.npy": [bench.DUMP_SAMPLE_PIXELS, 4], "image_sample_pixel.npy": [bench.DUMP_SAMPLE_PIXELS]}
+    idx = np.load(tmp_path / "a" / "image_sample_pixel.npy")
+    assert idx.dtype == np.float64 and np.array_equal(idx, np.load(tmp_path / "b" / "image_sample_pixel.npy"))
+    assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < 3840 * 2160
+    sample = np.load(tmp_path / "a" / "image_rgba_sample.npy")
+    assert sample.dtype == np.float32 and np.array_equal(sample, big.reshape(-1, 4)[idx.astype(np.int64)])
+    assert np.array_equal(np.load(tmp_path / "a" / "image_row_sums.npy"), big.reshape(2160, 3840, 4).sum(axis=1))
+    assert sum(os.path.getsize(p) for p in (tmp_path / "a").iterdir()) <= 64_000_000
+    assert not (tmp_path / "a" / "image_rgba.npy").exists()
+
+
+def test_bench_refuses_zero_steps():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 2 and "--steps must be at least 1" in p.stderr

@@ -7,12 +7,15 @@ of a synthetic scene whose geometry, layer table and styles are already resident
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME | --svg FILE [--svg-scale S]]
                     [--in-flight F] [--mode multi|exchange|bands|frames] [--no-animated] [--no-cpu-baseline]
-                    [--dump-outputs DIR]
+                    [--dump-outputs DIR] [--full]
 
 N = 1.  ONE renderer context — what a caller of `Renderer::render` has — renders exactly K frames; `value` = K / wall time.
 The context keeps `--in-flight` F frame slots (default 3, `forma_hip_set_frames_in_flight`): a device-resident frame is
 enqueued on the next slot and verified when the slot comes round, so the kernels of consecutive frames overlap on the GPU
-(they are bound by their own dependent round trips, not by a chip-wide resource).  Next to it, always:
+(they are bound by their own dependent round trips, not by a chip-wide resource).
+
+A plain run does only what `value` needs: it sets up, warms up, times the K steps, writes `--dump-outputs` and prints the
+line (`value`, `ms_per_step`, `mpixel_segments_per_s`, the configuration).  `--full` measures everything else as well:
   * `fps_render_call`: the same context with ONE frame in flight, every call complete when it returns — SURVEY §8(d)'s
     "1 / wall time of one render call" — with its latency, and `fps_including_d2h`: >= 60 such calls that also copy the
     33 MB image into caller memory (what `Renderer::render` promises; never `value`);
@@ -20,7 +23,9 @@ enqueued on the next slot and verified when the slot comes round, so the kernels
     HIP events at the stage boundaries on the context's stream — with frames overlapping, a launch duration is not the
     kernel's own;
   * `animated`: BASELINE config 5 (deterministic spaceship, 600 frames at 4K, with and without the buffer-layer cache);
-  * `cpu_baseline`: the C++ oracle on the same scene tables (`kind: "port"`).
+  * `cpu_baseline`: the C++ oracle on the same scene tables (`kind: "port"`);
+  * `fps_blocks`: five more blocks of K frames after the timed region;
+  * N > 1: both layouts of a multi-device context, and BASELINE config 4 (`second_workload`).
 `roofline.traffic`, `post_sort_traffic_ratio` and the painter's counters are measured in the run at N = 1 (three child runs of this command under
 `rocprofv3 --pmc`: the SQ counters, FETCH_SIZE, WRITE_SIZE; tools/pmc_round.py, ~15 s; `--no-pmc` skips them); without rocprofv3 it is read from the committed counter summary and labelled so.
 
@@ -94,6 +99,10 @@ def parse():
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write the image the last timed step rendered to DIR/*.npy (float32 / float64, at most "
                          "64 MB: the whole image when it fits, else a fixed seeded sample of its pixels; always its exact row sums)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, measure everything else too: one frame in flight, stage and kernel times, roofline "
+                         "and counters, the PCIe-inclusive legs, the animated scene, the CPU baseline; N > 1: both multi-device layouts "
+                         "and BASELINE config 4 (the --no-* options trim it)")
     ap.add_argument("--preflight", default=None, help=argparse.SUPPRESS)     # child process: try a multi-device context, print OK
     args = ap.parse_args()
     if args.steps < 1:
@@ -320,6 +329,54 @@ def main():
                 last_image = ctx.read_image(width, height)
             else:
                 print(f"bench.py --dump-outputs: --mode {mode} leaves one band of the image per rank; nothing written", file=sys.stderr)
+        sharding_txt = {
+            "single": "none",
+            "multi": f"ONE renderer context over {len(multi_devices)} GPUs (forma_hip_create_multi, driven by rank 0; per-device host threads inside "
+                     f"libforma_hip.so), tile-row bands of equal pixel-segment counts, every device writes its rows of the one caller buffer; layout "
+                     f"AUTO (forma_hip_multi_layout): BANDS = every device culls the whole scene to its band, no exchange; EXCHANGE = lines / "
+                     f"{len(multi_devices)} rasterized per GPU, HIP bucketing by tile-row owner, one RCCL all-to-all of pixel segments",
+            "frames": f"frame-parallel x{world}: every GPU renders whole frames of the workload (units = frames), no exchange",
+            "bands": f"tile-row bands x{world} of ONE frame, replicated scene, band culling, no data-path collective",
+            "exchange": f"ONE frame, one process per GPU: lines / {world} rasterized per GPU, HIP bucketing by tile-row owner, one RCCL all-to-all of "
+                        f"pixel segments (torch.distributed, padded equal split on the context's stream), band-local sort + paint"}[mode]
+        out = {
+            "metric": "frames/sec (sorted+painted, device-resident) + Mpixel-segments/sec",
+            "value": round(fps, 2), "unit": "frames/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+            "scaling": "weak" if mode in ("single", "frames") else "strong", "vs_baseline": None,
+            "dtype": "u64 segments / f64+f32 rasterizer / f32 painter", "data": "synthetic",
+            **({"rehearsal_backend": backend} if backend != "nccl" else {}),
+            **({"rehearsal_devices": multi_devices, "rehearsal": "ONE physical GPU listed several times: n_gpus counts device CONTEXTS, not GPUs"}
+               if mode == "multi" and len(set(multi_devices)) < len(multi_devices) else {}),
+            **({"launched": "in-process: one host process drives every GPU (no torchrun)"} if in_process else {}),
+            "value_is": (f"ONE renderer context, {in_flight} frames in flight inside it (forma_hip_set_frames_in_flight), one host thread"
+                         if mode == "single" else sharding_txt),
+            "mpixel_segments_per_s": round(n_segments_full * fps / 1e6, 1),
+            "frames_in_flight": in_flight,
+            "config": {"workload": workload + (" (labelled stand-in: paris-30k.svg is not in the reference checkout)"
+                                                     if workload.startswith("paris") else ""),
+                       "canvas": [width, height], "layers": len(comp), "pixel_segments": int(n_segments_full),
+                       "frames_in_flight": in_flight, "sharding": sharding_txt, "band_rows": [row0, row1]},
+            "full": args.full,
+        }
+
+        def finish():
+            if driver and ctx is not None:
+                try:
+                    out["context"] = ctx.info()                       # devices, frame slots, exchange transport (rccl / copy)
+                except Exception:                                     # noqa: BLE001
+                    pass
+            if last_image is not None:
+                out["dump_outputs"] = {"dir": args.dump_outputs, "files": dump_outputs(args.dump_outputs, last_image, width, height),
+                                       "what": "the RGBA8 image of the last timed step as float (dump_outputs() in bench.py)"}
+            if ctx is not None:
+                try:
+                    ctx.close()                                     # free the device buffers before the next workload
+                except Exception:
+                    pass
+            return out
+        if not args.full:                                           # a plain run: the headline figure and nothing else
+            return finish()
         blocks = [rate(args.steps, frames_per_step) for _ in range(5)]
         # the multi-device context's two layouts (forma_hip_multi_layout): `value` is the default's (AUTO), both are listed
         layouts = None
@@ -399,7 +456,7 @@ def main():
                     "algorithmic_bytes_per_launch": algo_bytes_per_pass, "avg_launch_us": round(pass_us, 2), "passes": passes,
                     "measured": f"HIP events carried by every k_onesweep launch (hipExtLaunchKernelGGL: the dispatch's own start and end) of "
                                 f"{acc.get('_frames', 0)} frames with ONE frame in flight, a further timed region of this run; matches `rocprofv3 "
-                                "--kernel-trace --stats -- python bench.py --in-flight 1 --no-d2h --no-animated --no-cpu-baseline`, profiles/r06g_kernel_stats_inflight1.csv"}
+                                "--kernel-trace --stats -- python bench.py --full --in-flight 1 --no-d2h --no-animated --no-cpu-baseline`, profiles/r06g_kernel_stats_inflight1.csv"}
         # the whole sort against the same roofline: histogram read + p digit passes = 8 N (2 p + 1) bytes — or 16 N p
         # when the histograms come out of the rasterizer's registers (read-back-free frames with <= 3 passes: k_sort_hist and its
         # read of the stream do not run; the counting costs k_rasterize ~13 us, which stays in the rasterize stage)
@@ -525,31 +582,8 @@ def main():
             for c, _ in extra:
                 c.close()
 
-        sharding_txt = {
-            "single": "none",
-            "multi": f"ONE renderer context over {len(multi_devices)} GPUs (forma_hip_create_multi, driven by rank 0; per-device host threads inside "
-                     f"libforma_hip.so), tile-row bands of equal pixel-segment counts, every device writes its rows of the one caller buffer; layout "
-                     f"AUTO (forma_hip_multi_layout): BANDS = every device culls the whole scene to its band, no exchange; EXCHANGE = lines / "
-                     f"{len(multi_devices)} rasterized per GPU, HIP bucketing by tile-row owner, one RCCL all-to-all of pixel segments",
-            "frames": f"frame-parallel x{world}: every GPU renders whole frames of the workload (units = frames), no exchange",
-            "bands": f"tile-row bands x{world} of ONE frame, replicated scene, band culling, no data-path collective",
-            "exchange": f"ONE frame, one process per GPU: lines / {world} rasterized per GPU, HIP bucketing by tile-row owner, one RCCL all-to-all of "
-                        f"pixel segments (torch.distributed, padded equal split on the context's stream), band-local sort + paint"}[mode]
         lat = 1e3 / statistics.median(blocks1)
-        out = {
-            "metric": "frames/sec (sorted+painted, device-resident) + Mpixel-segments/sec",
-            "value": round(fps, 2), "unit": "frames/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-            "scaling": "weak" if mode in ("single", "frames") else "strong", "vs_baseline": None,
-            "dtype": "u64 segments / f64+f32 rasterizer / f32 painter", "data": "synthetic",
-            **({"rehearsal_backend": backend} if backend != "nccl" else {}),
-            **({"rehearsal_devices": multi_devices, "rehearsal": "ONE physical GPU listed several times: n_gpus counts device CONTEXTS, not GPUs"}
-               if mode == "multi" and len(set(multi_devices)) < len(multi_devices) else {}),
-            **({"launched": "in-process: one host process drives every GPU (no torchrun)"} if in_process else {}),
-            "value_is": (f"ONE renderer context, {in_flight} frames in flight inside it (forma_hip_set_frames_in_flight), one host thread"
-                         if mode == "single" else sharding_txt),
-            "mpixel_segments_per_s": round(n_segments_full * fps / 1e6, 1),
-            "frames_in_flight": in_flight,
+        out.update({
             "fps_blocks": {"median": round(statistics.median(blocks), 1), "min": round(min(blocks), 1), "max": round(max(blocks), 1), "blocks": 5},
             "fps_render_call": {"median": round(statistics.median(blocks1), 1), "min": round(min(blocks1), 1), "max": round(max(blocks1), 1),
                                 "frame_latency_ms": round(lat, 4),
@@ -560,10 +594,6 @@ def main():
             "fps_including_d2h_frames": n_d2h,
             "fps_including_d2h_enqueued_three_buffers": fps_d2h_enqueue,
             "fps_including_d2h_three_contexts": fps_d2h_server,
-            "config": {"workload": workload + (" (labelled stand-in: paris-30k.svg is not in the reference checkout)"
-                                                     if workload.startswith("paris") else ""),
-                       "canvas": [width, height], "layers": len(comp), "pixel_segments": int(n_segments_full),
-                       "frames_in_flight": in_flight, "sharding": sharding_txt, "band_rows": [row0, row1]},
             "stages_us": {**{k: round(stage.get(k, 0.0), 1) for k in STAGE_KEYS}, "total_us": round(sum(stage.get(k, 0.0) for k in STAGE_KEYS), 1)},
             "stages_us_what": "a stage = the sum of its kernels' own durations (events carried by each launch: no marker overhead), total_us = "
                               "the sum of the stages = GPU time of a frame's kernels; compare with fps_render_call.frame_latency_ms (wall time of "
@@ -573,31 +603,18 @@ def main():
             "kernels_us": kernels_us,
             "roofline": roofline,
             "roofline_painter": painter,
-        }
+        })
         out["fps_one_frame_in_flight"] = out["fps_render_call"]       # (the name earlier rounds used)
         if layouts is not None:
             out["multi_layouts_fps"] = layouts
             out["multi_layouts_what"] = ("frames/s of the same multi-device context in both layouts (forma_hip_multi_layout): 'bands' = no exchange, every "
                                          "device culls the scene to its band of tile rows; 'exchange' = line shares + one all-to-all of pixel segments; "
                                          "`value` is the default layout's (AUTO picks per scene)")
-        if driver and ctx is not None:
-            try:
-                out["context"] = ctx.info()                           # devices, frame slots, exchange transport (rccl / copy)
-            except Exception:                                         # noqa: BLE001
-                pass
         if primary and rank == 0 and world == 1 and not args.no_animated and mode == "single":
             out["animated"] = animated_leg(local, args.animated_frames)
         if primary and rank == 0 and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(renderer, width, height, args.cpu_seconds)
-        if last_image is not None:
-            out["dump_outputs"] = {"dir": args.dump_outputs, "files": dump_outputs(args.dump_outputs, last_image, width, height),
-                                   "what": "the RGBA8 image of the last timed step as float (dump_outputs() in bench.py)"}
-        if ctx is not None:
-            try:
-                ctx.close()                                         # free the device buffers before the next workload
-            except Exception:
-                pass
-        return out
+        return finish()
 
     def agreed(ok):
         """every rank reports whether ITS attempt succeeded; the attempt counts only if all did"""
@@ -663,6 +680,8 @@ def main():
                str(args.warmup), "--workload", args.workload, "--mode", "exchange"]
         if args.dump_outputs:
             cmd += ["--dump-outputs", args.dump_outputs]
+        if args.full:
+            cmd += ["--full"]
         p = subprocess.run(cmd, capture_output=True, text=True)
         line = next((ln for ln in reversed(p.stdout.splitlines()) if ln.startswith("{")), None)
         if p.returncode != 0 or line is None:
@@ -675,14 +694,14 @@ def main():
         raise SystemExit(f"every mode failed: {errors}")
     if errors:
         out["mode_fallback_errors"] = errors
-    if rank == 0 and world == 1 and args.gpus == 1 and not args.no_pmc and not args.svg and args.workload == "paris-like-30k-4k" \
+    if args.full and rank == 0 and world == 1 and args.gpus == 1 and not args.no_pmc and not args.svg and args.workload == "paris-like-30k-4k" \
             and isinstance(out.get("roofline"), dict):
         live = live_traffic(out)
         if live is not None:
             out["roofline"].update(live["roofline"])
             if isinstance(out.get("roofline_painter"), dict):
                 out["roofline_painter"].update(live["roofline_painter"])
-    if sharded and not args.svg and args.workload != "triangles-10m-8k" and out["scaling"] == "strong":
+    if args.full and sharded and not args.svg and args.workload != "triangles-10m-8k" and out["scaling"] == "strong":
         # N > 1: the same sharded mode on BASELINE config 4 (10 M pixel segments at 8192 x 8192), the configuration the multi-GPU
         # target is quoted on; its numbers ride in the same JSON line
         try:

@@ -111,6 +111,16 @@ def test_dump_outputs_writes_the_whole_image_or_a_fixed_sample_within_64_mb(tmp_
     assert not (tmp_path / "a" / "image_rgba.npy").exists()
 
 
+def test_counter_child_runs_are_full_bench_runs(monkeypatch):
+    import bench
+    pmc_round = importlib.import_module("pmc_round")
+    assert "--full" in pmc_round.BENCH                 # (a plain run renders too few frames for the means the counters are taken over)
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    assert bench.parse().full is True
+
+
 def test_bench_refuses_zero_steps():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
     assert p.returncode == 2 and "--steps must be at least 1" in p.stderr

@@ -10,7 +10,7 @@ whose only traffic is one read of the 8 N byte stream).  Values are means over t
 import collections, csv, glob, json, os, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BENCH = ["python", os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--in-flight", "1", "--no-cpu-baseline", "--no-animated", "--no-d2h", "--no-pmc"]
+BENCH = ["python", os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--in-flight", "1", "--no-cpu-baseline", "--no-animated", "--no-d2h", "--no-pmc"]
 PASSES = [["SQ_INSTS_VALU", "SQ_INSTS_SALU", "SQ_INSTS_LDS", "SQ_LDS_BANK_CONFLICT", "SQ_LDS_IDX_ACTIVE", "SQ_WAIT_INST_LDS", "SQ_WAVES", "SQ_BUSY_CYCLES"],
           ["FETCH_SIZE"], ["WRITE_SIZE"]]
 
@@ -65,7 +65,7 @@ def main():
             v[c] = round(v[c], 1) if isinstance(v[c], float) else v[c]
 
     cal = kern.get("k_runs_count", {}).get("FETCH_SIZE", 0) * 1024 * 2 / (8.0 * n) if n else 0
-    json.dump({"_note": "rocprofv3 --pmc, three passes of `bench.py --steps 3 --warmup 1 --in-flight 1 --no-cpu-baseline`; mean over the "
+    json.dump({"_note": "rocprofv3 --pmc, three passes of `bench.py --full --steps 3 --warmup 1 --in-flight 1 --no-cpu-baseline`; mean over the "
                         "frame-sized dispatches; FETCH_SIZE / WRITE_SIZE in KB per dispatch, hbm_bytes_per_launch = 2 x FETCH + WRITE "
                         "(gfx950 FETCH_SIZE correction; calibration on k_runs_count, one read of the 8N-byte stream: measured / expected "
                         "= %.3f); SQ_* are sums over all waves of a dispatch" % cal,

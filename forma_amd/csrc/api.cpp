@@ -54,6 +54,7 @@ int reset_info(forma_hip_ctx* ctx) {              // device-to-device from a tem
     // (a read-back-free frame ends with k_frame_tail, which leaves the device copy pristine: the next frame's reset is free)
     if (!ctx->info_clean) HIPCHECK(hipMemcpyAsync(ctx->info.p, ctx->info_init.p, sizeof(FrameInfo), hipMemcpyDeviceToDevice, ctx->stream));
     ctx->info_clean = false;
+    ctx->seg_u_fused = false;
     return FORMA_OK;
 }
 // the end of a read-back-free frame: FrameInfo to pinned host memory (and / or the segment count to a pinned word), device copy reset
@@ -130,6 +131,7 @@ int finish_rasterize(forma_hip_ctx* ctx) {
 }
 
 SortPlan frame_sort_plan(forma_hip_ctx* ctx, uint64_t live44, bool layer_sorted, int digit_bits, bool speculated, bool* biased);
+static bool fuse_plan_ok(const forma_hip_ctx* ctx, const SortPlan& plan);
 
 // stages 1-2 on the uploaded geometry: line table + rasterize -> seg_u.
 // bound_n != 0: fully asynchronous (no read-back): N is only known to the device, buffers / grids are provisioned for
@@ -141,7 +143,7 @@ int run_rasterize_frame(forma_hip_ctx* ctx, uint32_t width, uint32_t height, boo
     const size_t n_lines = ctx->line_ranged ? std::min(ctx->line_hi, all_lines) - std::min(ctx->line_lo, all_lines) : all_lines;
     ctx->n_lines = n_lines;
     ctx->n_seg = 0; ctx->n_compact = 0; ctx->have_unsorted = true; ctx->live44 = 0; ctx->layer_sorted = true;
-    ctx->speculated = false; ctx->ras_hist_on = false;
+    ctx->speculated = false; ctx->ras_hist_on = false; ctx->ras_fused = false;
     ctx->pz = forma_hip_ctx::PreZero();                   // (nothing of this frame has been cleared ahead of its stage yet)
     int rc = reset_info(ctx);
     if (rc) return rc;
@@ -171,6 +173,13 @@ int run_rasterize_frame(forma_hip_ctx* ctx, uint32_t width, uint32_t height, boo
         ctx->ras_plan = frame_sort_plan(ctx, ctx->pred_live44, ctx->pred_layer_sorted, ctx->digit_bits, true, nullptr);
         RH = make_ras_hist(ctx->ras_plan, ctx->sort_counters.as<uint32_t>());
         ctx->ras_hist_on = RH.hist != nullptr;
+        // ... and the first digit pass with them, where the frame's first kernel cleared the slice table for this bound
+        if (RH.hist && ctx->pz.slice_p && ctx->pz.slice_p == ctx->slice_buf.p && ctx->pz.slice_words >= slice_tab_words(bound_n) &&
+            fuse_plan_ok(ctx, ctx->ras_plan)) {
+            const SliceSrc SS = make_slice_src(ctx->slice_buf.as<uint32_t>(), bound_n);
+            RH.slice_tab = SS.tab; RH.tab_stride = SS.tab_stride;
+            ctx->ras_fused = true;
+        }
         // the tile fields' spans are worth measuring only where a biased plan could ever beat the plain one: the plain digits of
         // the tile fields take more than two passes (canvases beyond 255 tiles in a dimension), or this frame's plan is biased
         // already (its digits are checked against the spans).  4K and below: no — 80 VALU instructions per rasterizer lane less.
@@ -188,6 +197,7 @@ int run_rasterize_frame(forma_hip_ctx* ctx, uint32_t width, uint32_t height, boo
                      (int)ctx->band_row1, ctx->ras_masks.as<uint32_t>(), /*reduce_now=*/bound_n == 0, &RH);
     // read-back-free frame: the masks stay per-workgroup records until k_runs_count combines them (nothing reads them earlier)
     ctx->pending_masks = bound_n ? PendingMasks{ctx->ras_masks.as<uint32_t>(), 0u, ctx->ras_hist_on ? 1u : 0u} : PendingMasks{nullptr, 0u, 0u};
+    ctx->seg_u_fused = ctx->ras_fused; ctx->fused_w = width; ctx->fused_h = height;
     stage_end(ctx, ST_RASTER, timing);
     HIPCHECK(hipGetLastError());
     ctx->speculated = (speculate || bound_n) && ctx->pred_valid;
@@ -269,6 +279,37 @@ SortPlan frame_sort_plan(forma_hip_ctx* ctx, uint64_t live44, bool layer_sorted,
     return make_segment_sort_plan(live44, layer_sorted, digit_bits, range, biased);
 }
 
+// The sort's first digit pass fused into the rasterizer (SliceSrc): a 2 048-segment block leaves k_rasterize partitioned by the
+// plan's first digit, and the next pass reads that stream in logical order through the list of its (digit, block) slices —
+// one read and one write of the whole stream less.  Read-back-free frames only (the plan must be known before the rasterizer
+// runs; a wrong one voids the frame like a wrong bias does), plans of 2 .. RH_MAX_PASSES passes whose first digit has at most
+// 256 bins, whole frames (no band, no line range).  A pass that gathers slices of a few keys reads HBM in short pieces: below
+// FUSE_MIN_SLICE keys per slice on the last fused frame (geometry scattered over many tiles per block) the plain pass is kept:
+// tools/fuse_sweep.py (profiles/fuse_digit_threshold_sweep.json) — rasterizer + sort, fused against plain, 4K: -0.5 us at 17 keys,
+// -0.6 at 24, +1.5 at 30, +3.5 .. +4.3 at 40 .. 53, +14.2 on the headline scene (65).
+// FORMA_HIP_DEBUG=fuse_digit=0|2: never / always.
+#ifndef FUSE_MIN_SLICE
+#define FUSE_MIN_SLICE 28
+#endif
+// A context whose slices were too short probes again every FUSE_PROBE frames (one fused frame re-measures them): the geometry
+// may have changed under unchanged tables (transforms).
+#ifndef FUSE_PROBE
+#define FUSE_PROBE 256
+#endif
+static bool fuse_plan_ok(const forma_hip_ctx* ctx, const SortPlan& plan) {
+    if (ctx->dbg.fuse_digit == 0 || ctx->dbg.no_ras_hist || ctx->digit_bits == 4) return false;
+    if (ctx->band_row1 > 0 || ctx->line_ranged) return false;
+    return plan.n_passes >= 2 && plan.n_passes <= RH_MAX_PASSES && plan.mask[0] <= 255u;
+}
+// decided once per frame, by plan_zero_jobs (the slice table is cleared only for a frame that fuses)
+static bool fuse_first_digit(forma_hip_ctx* ctx, const SortPlan& plan) {
+    if (!fuse_plan_ok(ctx, plan)) return false;
+    if (ctx->dbg.fuse_digit == 2 || ctx->pred_slice_len == 0 || ctx->pred_slice_len >= FUSE_MIN_SLICE) return true;
+    if (++ctx->fuse_skipped < FUSE_PROBE) return false;
+    ctx->fuse_skipped = 0;
+    return true;
+}
+
 // What the frame's FIRST kernel (k_line_len) clears for the later stages of a read-back-free frame — the sort's histograms,
 // tickets and status rows, the tile tables — instead of memset operations on the stream: a
 // band frame of a multi-device context is ~250 us of kernels, and every stream operation costs the host ~5 us and the device a
@@ -292,6 +333,12 @@ int plan_zero_jobs(forma_hip_ctx* ctx, uint32_t width, uint32_t height, uint32_t
     // (the status words of the chained run kernel: a word per 2 048 segments)
     const size_t cw = runs_n ? runs_chain_words(runs_n) : 0;
     if (cw && cw <= 0xFFFFFFFFull) { Z->p[Z->n] = ctx->runs_scratch.as<uint32_t>(); Z->words[Z->n++] = (uint32_t)cw; cleared->chain_p = ctx->runs_scratch.p; cleared->chain_words = cw; }
+    // (the slice table of a fused first digit pass)
+    if (sw && Z->n < FORMA_ZERO_JOBS && fuse_first_digit(ctx, plan) && slice_tab_words(sort_n) <= 0xFFFFFFFFull) {
+        HIPCHECK(ctx->slice_buf.ensure(slice_scratch_words(sort_n) * 4));
+        const size_t lw = slice_tab_words(sort_n);
+        Z->p[Z->n] = ctx->slice_buf.as<uint32_t>(); Z->words[Z->n++] = (uint32_t)lw; cleared->slice_p = ctx->slice_buf.p; cleared->slice_words = lw;
+    }
     return FORMA_OK;
 }
 
@@ -318,12 +365,20 @@ int run_sort(forma_hip_ctx* ctx, const uint64_t* src, DevCount nc, bool timing, 
                      plan.fmask[p] == ctx->ras_plan.fmask[p];
     if (ctx->ras_hist_on && !hist_ready) zeroed = false;
     ctx->ras_hist_on = false;
+    // the rasterizer partitioned its blocks by the first digit: only the sort it planned for may read them (never met: the plan is
+    // the same function of the same predictions; should it differ, the frame is void and runs again synchronously)
+    const bool fused = ctx->ras_fused && hist_ready;
+    if (ctx->ras_fused && !fused) HIPCHECK(hipMemsetAsync(&ctx->info.as<FrameInfo>()->plan_bad, 1, 4, ctx->stream));
+    ctx->ras_fused = false;
+    SliceSrc SS;
+    if (fused) SS = make_slice_src(ctx->slice_buf.as<uint32_t>(), n);
     if (hist_ready) ctx->sort_range = nullptr;               // (the spans travel in the rasterizer's mask records: PendingMasks::has_range)
     stage_begin(ctx, ST_SORT, timing);
     ctx->sorted = (uint64_t*)launch_radix_sort(ctx->stream, src, ctx->seg_a.as<uint64_t>(), ctx->seg_b.as<uint64_t>(), nc, plan,
                                                digit_bits, ctx->sort_counters.as<uint32_t>(), &ctx->info.as<FrameInfo>()->error,
                                                chunked,
-                                               ctx->info.as<FrameInfo>(), zeroed, hist_ready, sort_workgroups(ctx, n));
+                                               ctx->info.as<FrameInfo>(), zeroed, hist_ready, sort_workgroups(ctx, n),
+                                               fused ? &SS : nullptr);
     stage_end(ctx, ST_SORT, timing);
     HIPCHECK(hipGetLastError());
     return FORMA_OK;
@@ -951,6 +1006,7 @@ int finish_frame(forma_hip_ctx* ctx, forma_timings_t* t, bool have_info = false)
         ctx->pred_range = KeyRange{~r[0], r[1], ~r[2], r[3], true};
     }
     if (!ctx->h_info->plan_bad) ctx->pred_row_spans = ctx->h_info->n_spans / ctx->cur_rows_painted;
+    if (!ctx->h_info->plan_bad && ctx->h_info->n_slices) ctx->pred_slice_len = std::max(ctx->h_info->n_segments / ctx->h_info->n_slices, 1u);
     if (!ctx->h_info->plan_bad) { ctx->pred_max_slice = ctx->h_info->max_slice_runs; ctx->pred_slice_n = ctx->cur_slices; ctx->pred_slice_small = ctx->cur_small; ctx->pred_slice_half = ctx->cur_half; }
     if ((ctx->h_info->error & ~24u) == 1u)                   // (bit 0: k_carry_rows met a run of a layer without a style)
         return fail(ctx, FORMA_E_ARG, "a geometry entry names an order that has no style (forma_hip_set_styles: offset FORMA_NONE or beyond the table)");
@@ -1170,6 +1226,9 @@ int forma_hip_set_geoms(forma_hip_ctx* ctx, const forma_geom_t* geoms, size_t n_
     if ((rc = upload(ctx, ctx->geoms, geoms, n_geoms))) return rc;
     HIPCHECK(hipStreamSynchronize(ctx->stream));
     ctx->n_geoms = n_geoms; ctx->max_geom_order = max_order;
+    // (transforms move the lines: a fused frame's unsorted stream can no longer be rebuilt from them — restore_unsorted)
+    if (ctx->seg_u_fused) { ctx->seg_u_fused = false; ctx->have_unsorted = false; }
+    for (forma_hip_ctx* sl : ctx->slots) if (sl->seg_u_fused) { sl->seg_u_fused = false; sl->have_unsorted = false; }
     share_scene(ctx);
     return FORMA_OK;
 }
@@ -1375,6 +1434,7 @@ int forma_hip_sort(forma_hip_ctx* ctx, uint64_t* segments, size_t n, int digit_b
     HIPCHECK(hipSetDevice(ctx->device));
     HIPCHECK(ctx->seg_u.ensure((n + SEG_PAD) * 8));
     HIPCHECK(hipMemcpyAsync(ctx->seg_u.p, segments, n * 8, hipMemcpyHostToDevice, ctx->stream));
+    ctx->seg_u_fused = false;
     ctx->live44 = host_live44(segments, n);
     ctx->layer_sorted = false;
     ctx->pz = forma_hip_ctx::PreZero();
@@ -1431,7 +1491,8 @@ int poison_frame_buffers(forma_hip_ctx* c) {
     DevBuf* frame[] = {&c->scan_tmp, &c->cl_idx, &c->cl_start, &c->block_first, &c->prep_scratch, &c->seg_u, &c->seg_a, &c->seg_b,
                        &c->sort_counters, &c->records, &c->rk_u, &c->rk_a, &c->rk_b, &c->blk_edge, &c->runs_scratch, &c->row_tab,
                        &c->span_key, &c->span_cov, &c->ras_masks, &c->huge_offs, &c->huge_key, &c->huge_tmp, &c->huge_flag,
-                       &c->grp_tab, &c->grp_list, &c->run_lt, &c->rec_sp, &c->run_lt_sp, &c->row_sp, &c->pack_list, &c->pack_pix};
+                       &c->grp_tab, &c->grp_list, &c->run_lt, &c->rec_sp, &c->run_lt_sp, &c->row_sp, &c->pack_list, &c->pack_pix,
+                       &c->slice_buf};
     for (DevBuf* b : frame) if (b->p && !b->borrowed) HIPCHECK(hipMemsetAsync(b->p, byte, b->cap, c->stream));
     return FORMA_OK;
 }
@@ -1610,8 +1671,11 @@ void share_scene(forma_hip_ctx* o) {
 }
 void invalidate_counts(forma_hip_ctx* o) {                 // new geometry / band: every slot re-learns N and J synchronously
     o->pred_counts_valid = false; o->xpred_valid = false; o->small_banned = false; o->covl_banned = false; o->bias_banned = 0; o->bias_ban_len = 0; o->pred_range.valid = false;
-    o->order_off = 0; o->order_flat = 0; o->order_cur = -1; o->cull_on = false;
-    for (forma_hip_ctx* sl : o->slots) { sl->order_off = 0; sl->order_flat = 0; sl->order_cur = -1; sl->cull_on = false; }
+    o->order_off = 0; o->order_flat = 0; o->order_cur = -1; o->cull_on = false; o->pred_slice_len = 0;
+    for (forma_hip_ctx* sl : o->slots) { sl->order_off = 0; sl->order_flat = 0; sl->order_cur = -1; sl->cull_on = false; sl->pred_slice_len = 0; }
+    // a fused frame's unsorted stream is rebuilt from the scene's CURRENT lines and band (restore_unsorted): gone with them
+    if (o->seg_u_fused) { o->seg_u_fused = false; o->have_unsorted = false; }
+    for (forma_hip_ctx* sl : o->slots) if (sl->seg_u_fused) { sl->seg_u_fused = false; sl->have_unsorted = false; }
     for (forma_hip_ctx* sl : o->slots) { sl->pred_counts_valid = false; sl->xpred_valid = false; sl->small_banned = false; sl->covl_banned = false; sl->bias_banned = 0; sl->bias_ban_len = 0; sl->pred_range.valid = false; }
 }
 }  // namespace
@@ -1795,7 +1859,7 @@ int forma_hip_trim(forma_hip_ctx* ctx) {
                            &c->sort_counters, &c->records, &c->rk_u, &c->rk_a, &c->rk_b, &c->blk_edge, &c->runs_scratch, &c->row_tab,
                            &c->span_key, &c->span_cov, &c->image, &c->xscratch, &c->ras_masks, &c->xmask,
                            &c->huge_offs, &c->huge_key, &c->huge_tmp, &c->huge_flag, &c->grp_tab, &c->grp_list, &c->run_lt, &c->rec_sp, &c->run_lt_sp, &c->row_sp, &c->pack_list, &c->pack_pix,
-                           &c->order_buf};
+                           &c->order_buf, &c->slice_buf};
         c->order_cur = -1; c->order_pending = -1; c->order_cnt_dev = nullptr; c->order_keep_dev = nullptr;
         size_t freed = 0;
         for (DevBuf* b : frame) { if (!b->borrowed) freed += b->cap; b->release(); }
@@ -1872,6 +1936,21 @@ int forma_hip_tiles_written(forma_hip_ctx* ctx, uint8_t* flags, size_t n_tiles) 
 }  // extern "C"
 
 // the stream / the written-tile flags of exactly this context's last frame (no slot resolution: multi.cpp names the slot)
+// A frame with the first digit pass fused left its blocks in seg_u partitioned by that digit.  Whoever asks for the unsorted
+// stream gets it in stream order: the frame's blocks are rasterized once more from its line table (inspection only, never on
+// the frame path).
+int restore_unsorted(forma_hip_ctx* ctx) {
+    if (!ctx->seg_u_fused || !ctx->n_seg) return FORMA_OK;
+    const LineSource S = geometry_source(ctx, ctx->fused_w, ctx->fused_h);
+    launch_rasterize(ctx->stream, S, DevCount{nullptr, ctx->h_info->n_compact}, DevCount{nullptr, (uint32_t)ctx->n_seg},
+                     ctx->cl_idx.as<uint32_t>(), ctx->cl_start.as<uint32_t>(), ctx->block_first.as<uint32_t>(), ctx->seg_u.as<uint64_t>(),
+                     ctx->info.as<FrameInfo>(), (int)ctx->band_row0, (int)ctx->band_row1, ctx->ras_masks.as<uint32_t>(), /*reduce_now=*/false, nullptr);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(ctx->stream));
+    ctx->seg_u_fused = false;
+    return FORMA_OK;
+}
+
 int fd_read_stream(forma_hip_ctx* ctx, int which, uint64_t* out, size_t capacity, size_t* out_n) {
     *out_n = ctx->n_seg;
     if (which == 0 && !ctx->have_unsorted) return fd_fail(ctx, FORMA_E_STATE, "no unsorted stream on the device");
@@ -1879,6 +1958,7 @@ int fd_read_stream(forma_hip_ctx* ctx, int which, uint64_t* out, size_t capacity
     if (ctx->n_seg == 0) return FORMA_OK;
     if (!out) return FORMA_E_ARG;
     HIPCHECK(hipSetDevice(ctx->device));
+    if (which == 0) { const int rc = restore_unsorted(ctx); if (rc) return rc; }
     const void* src = which == 0 ? ctx->seg_u.p : (const void*)ctx->sorted;
     if (!src) return fd_fail(ctx, FORMA_E_STATE, "no segments on the device");
     HIPCHECK(hipMemcpy(out, src, ctx->n_seg * 8, hipMemcpyDeviceToHost));
@@ -1926,6 +2006,7 @@ int forma_hip_set_band(forma_hip_ctx* ctx, uint32_t row0, uint32_t row1) {
 int forma_hip_segments_device(forma_hip_ctx* ctx, int which, uint64_t** dev_ptr, size_t* n) {
     if (!ctx || !dev_ptr || !n) return FORMA_E_ARG;
     ENTER_SINGLE(ctx);
+    if (which == 0) { HIPCHECK(hipSetDevice(ctx->device)); const int rc = restore_unsorted(ctx); if (rc) return rc; }
     *dev_ptr = which == 0 ? ctx->seg_u.as<uint64_t>() : ctx->sorted;
     *n = ctx->n_seg;
     return FORMA_OK;

@@ -53,6 +53,7 @@ struct FrameInfo {
     uint32_t tile_range[4];       // of the sorted keys' tile fields, as maxima: ~min(tile_x + 1), max(tile_x + 1), ~min(tile_y + 1), max(tile_y + 1)
     uint32_t n_heavy;             // tiles the painters filed as heavy this frame (PaintParams::order_*; summed by k_frame_tail)
     uint32_t cost_sum, cost_n;    // ... and a 1-in-256 sample of what a tile cost: shader clocks >> 8, tiles sampled
+    uint32_t n_slices;            // fused first digit (SliceSrc): non-empty (digit, block) slices of the rasterized stream, 0 if not fused
 };
 
 // one run of the sorted stream = one painted (tile, layer) pair that owns pixel segments
@@ -232,7 +233,9 @@ void launch_block_first(hipStream_t s, const uint32_t* cl_start, uint32_t n_comp
 #define RH_MAX_PASSES 3
 struct RasHist { uint32_t* hist; uint32_t n_passes; uint32_t shift[RH_MAX_PASSES], mask[RH_MAX_PASSES], bias[RH_MAX_PASSES], fmask[RH_MAX_PASSES];
                  uint32_t track_range; /* also measure what the keys' tile fields span (KeyRange for the next frame's plan): only
-                                          where a field taken relative to its minimum can save a digit pass — else the records say "unknown" */ };
+                                          where a field taken relative to its minimum can save a digit pass — else the records say "unknown" */
+                 uint32_t* slice_tab; uint32_t tab_stride; /* != nullptr: the first digit pass is fused (SliceSrc) — each RAS_TILE block is
+                                          written partitioned by digit 0, its slices to slice_tab[d * tab_stride + b] */ };
 void launch_rasterize(hipStream_t s, const LineSource& src, DevCount n_compact, DevCount n_segments,
                       const uint32_t* cl_idx, const uint32_t* cl_start, const uint32_t* block_first, uint64_t* out,
                       FrameInfo* info, int band_row0, int band_row1, uint32_t* wg_masks /* 8 words per RAS_TILE block */,
@@ -269,6 +272,8 @@ const uint32_t* sort_range_words(const uint32_t* scratch);  // per k_sort_hist w
 // k_sort_hist and the first digit pass read it in place (logical index -> bucket by <= 7 compares), which removes the
 // gather kernel; k_sort_hist also publishes the total (info->n_segments), the overflow flag and, per workgroup, the key
 // masks / layer-order bit the sort plan is verified with (mask_records, 8 words each: PendingMasks).  n_chunks == 0: plain.
+struct SliceSrc {   // the fused first digit pass (see make_slice_src)
+    uint32_t* tab; uint32_t tab_stride; uint32_t* first; uint32_t first_cap; uint2* ent; uint32_t ent_cap; };
 struct ChunkedSrc { const uint64_t* buckets; uint32_t n_chunks; uint32_t capacity; uint32_t* mask_records; };
 uint32_t sort_hist_blocks(size_t n);           // grid of k_sort_hist for n keys = number of mask records it writes
 const uint64_t* launch_radix_sort(hipStream_t s, const uint64_t* in, uint64_t* a, uint64_t* b, DevCount n,
@@ -276,8 +281,19 @@ const uint64_t* launch_radix_sort(hipStream_t s, const uint64_t* in, uint64_t* a
                                   const ChunkedSrc* chunked = nullptr, FrameInfo* info = nullptr,
                                   bool scratch_is_zero = false /* an earlier kernel of the frame cleared sort_zero_words() */,
                                   bool hist_ready = false /* ... and the producer of the keys counted the digits (RasHist) */,
-                                  uint32_t max_workgroups = 0 /* 0: one persistent workgroup per CU; else at most this many */);
+                                  uint32_t max_workgroups = 0 /* 0: one persistent workgroup per CU; else at most this many */,
+                                  const SliceSrc* sliced = nullptr /* the first pass was fused into the rasterizer (needs hist_ready) */);
 RasHist make_ras_hist(const SortPlan& plan, uint32_t* sort_scratch);      // hist == nullptr if the plan does not qualify
+// The first digit pass fused into the rasterizer (read-back-free frames, plans of >= 2 passes whose first digit has <= 256 bins):
+// k_rasterize writes each RAS_TILE block of keys stably partitioned by digit 0 and, per non-empty (digit d, block b) slice, the
+// word (local offset << 12) | count at tab[d * tab_stride + b] (the table is cleared by the frame's first kernel); it also counts
+// digit 0 and the blocks holding each digit into the histogram copies (rows 0 and SLICE_NZ_ROW).  k_slice_scan turns the table
+// into the list of the non-empty slices in digit-major order — {first logical index, physical - logical} each, a sentinel behind
+// the last — and the first slice of every tile of the next pass; that pass reads the logical stream in place.
+#define SLICE_NZ_ROW (SORT_MAX_PASSES - 1)
+size_t slice_scratch_words(size_t n);                 // [tab: 256 x stride] [first: tiles + 2] [ent: 2 x cap]
+size_t slice_tab_words(size_t n);                     // the leading words that must be zero when the frame starts
+SliceSrc make_slice_src(uint32_t* scratch, size_t n);
 
 // exchange.hip — multi-GPU: bucket a rank's pixel segments by tile-row owner, gather what the owner received
 #define FORMA_MAX_RANKS 8

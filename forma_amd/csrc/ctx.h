@@ -86,6 +86,7 @@ struct forma_hip_ctx {
     bool cur_half = false, pred_slice_half = false;   // the 512-lane variant of the small carry kernel (api.cpp run_paint)
     bool cur_small = false, pred_slice_small = false, small_tried = false, small_banned = false, no_small_carry = false;
     bool covl_tried = false, covl_banned = false;   // the COVL carry variant (rows' covers in LDS) was this read-back-free frame's guess / a frame that guessed it was void
+    DevBuf slice_buf;                       // fused first digit pass (SliceSrc): slice table, tiles' first slices, slice list
     DevBuf ras_masks;                       // k_rasterize: key masks per workgroup (8 words), combined by k_reduce_masks
     PendingMasks pending_masks{nullptr, 0u}; // ... or, on read-back-free frames, by k_runs_count
     size_t n_lines = 0, n_compact = 0;
@@ -139,6 +140,10 @@ struct forma_hip_ctx {
     KeyRange pred_range{0, 0, 0, 0, false};  // what the tile fields spanned on the last verified frame (value-range digits, SortPlan::bias)
     bool plan_biased = false; uint32_t bias_banned = 0, bias_ban_len = 0;   // bias_banned: frames left of a ban (re-armed with back-off: an animated scene
                                                       // that left its span once gets the cheaper plan back), bias_ban_len: length of the last ban //   // this frame's plan leans on pred_range / a frame that did was void: plain digits for this geometry
+    bool seg_u_fused = false; uint32_t fused_w = 0, fused_h = 0;   // seg_u holds a fused frame's partitioned blocks (restore_unsorted)
+    bool ras_fused = false;                 // ... and wrote its blocks partitioned by ras_plan's first digit (SliceSrc)
+    uint32_t pred_slice_len = 0;            // mean keys per (digit, block) slice of the last fused frame (0: not measured)
+    uint32_t fuse_skipped = 0;              // frames not fused since the slices were measured too short (FUSE_PROBE)
     bool ras_hist_on = false; SortPlan ras_plan;     // the rasterizer of this frame counted the digits of ras_plan into the sort's histograms (RasHist)
     const uint32_t* sort_range = nullptr;   // the tile-field spans the frame's sort leaves behind (k_runs_count folds them into FrameInfo) ...
     uint32_t sort_range_n = 0;              // ... one record per k_sort_hist workgroup
@@ -151,7 +156,7 @@ struct forma_hip_ctx {
     // what this frame's FIRST kernel cleared on behalf of later stages (ZeroJobs, common.h): consumed by run_sort / run_paint,
     // which clear the words themselves when the pointer or the size is not what they need
     struct PreZero { const void* sort_p = nullptr; size_t sort_words = 0; const void* tab_p = nullptr; size_t tab_words = 0;
-                     const void* chain_p = nullptr; size_t chain_words = 0; } pz;
+                     const void* chain_p = nullptr; size_t chain_words = 0; const void* slice_p = nullptr; size_t slice_words = 0; } pz;
     ForMaDebug dbg;                         // FORMA_HIP_DEBUG as it stood when the context was created
     const uint32_t* chain_rows = nullptr;   // this frame's runs were numbered per tile row (launch_runs' chain): its row counts, for the
     uint32_t n_chain_rows = 0;              //   frame tail, which sums them into the host's n_runs

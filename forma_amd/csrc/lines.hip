@@ -4,6 +4,7 @@
 // writes `mul_add`.  All kernels are HBM/L2-bound integer + f32/f64 scalar work: no MFMA.
 #include "common.h"
 #include "lookback.h"
+#include "radix_rank.h"
 #include <string.h>
 #ifdef RAS_PROF
 // -DRAS_PROF (tools only): shader-clock stamps at the phase boundaries of k_rasterize (thread 0 of every workgroup)
@@ -585,7 +586,94 @@ __device__ __forceinline__ LineP load_line(const LineSource& S, uint32_t li) {
 #ifndef RAS_OCC
 #define RAS_OCC 6             // waves per SIMD the kernel is compiled for (<= 80 VGPRs: the three-round staging alone took 82 = five)
 #endif
-template <bool HIST>         // HIST = false is the plain kernel, instruction for instruction
+// The line window of a workgroup.  FUSE: once the last line is done it holds the block's 2 048 keys (16 KB) while they are
+// partitioned by the sort's first digit — no LDS beyond what the kernel had (six workgroups per CU).
+struct RasWindow {
+    double aab[RAS_WIN], bab[RAS_WIN], cdab[RAS_WIN], cdb[RAS_WIN];     // find's constants per line (find_term_k)
+    float x0[RAS_WIN], y0[RAS_WIN], dx[RAS_WIN], dy[RAS_WIN], a[RAS_WIN], b[RAS_WIN], c[RAS_WIN], d[RAS_WIN];
+    uint32_t start[RAS_WIN + 1], order[RAS_WIN];
+    int ioff[RAS_WIN];                                                   // start - ioff: segment k of the line has i = k - w_ibase
+};
+union RasLds { RasWindow w; uint64_t stg[RAS_TILE]; };
+static_assert(sizeof(uint64_t) * RAS_TILE <= sizeof(RasWindow), "the partition staging lives in the line window");
+
+// FUSE: the block's keys leave stably partitioned by the sort's first digit — ranked like a digit pass does it (rows of 64
+// consecutive keys, match-any, per-wave 16-bit counters in lh's first row, which the fused kernel does not count into), staged
+// in the dead line window, stored in 16-byte pieces.  Thread d < 256 then files the block's slice of digit d in the table and
+// counts it (digit 0's histogram and its blocks: what k_slice_scan needs for the logical positions).
+__device__ __forceinline__ void ras_partition(const uint64_t (&vout)[RAS_PER_THREAD], uint64_t* __restrict__ out, const RasHist& RH,
+                                              uint64_t* stg, uint16_t* wc /* [waves][256], cleared */, uint32_t* wsum /* [waves] */,
+                                              uint32_t k0, uint32_t k1) {
+    constexpr int WAVES = RAS_THREADS / 64, PER_WAVE = 64 * RAS_PER_THREAD;
+    static_assert(WAVES * 256 * 2 <= SORT_BINS * 4, "the wave counters live in lh's first row");
+    static_assert(RAS_THREADS == 256, "one digit per thread");
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const uint32_t sh = RH.shift[0], mk = RH.mask[0], bs = RH.bias[0];
+    const uint32_t nloc = k1 - k0;
+#pragma unroll
+    for (int q = 0; q < RAS_PER_THREAD; q += 2)
+        *reinterpret_cast<ulonglong2*>(&stg[tid * RAS_PER_THREAD + q]) = make_ulonglong2(vout[q], vout[q + 1]);
+    __syncthreads();
+    uint64_t kk[RAS_PER_THREAD];
+    uint32_t rk[RAS_PER_THREAD / 2];                                    // 16-bit ranks, two per register
+    uint32_t* wcw = reinterpret_cast<uint32_t*>(wc) + w * 128;
+#pragma unroll
+    for (int j = 0; j < RAS_PER_THREAD; j++) {
+        const uint32_t i = w * PER_WAVE + j * 64 + lane;
+        kk[j] = stg[i];
+        // padding (the last block's positions >= nloc): the LAST digit, so that it ranks behind every key of the block; it is
+        // taken off that digit's count below and never stored
+        const uint32_t dg = i < nloc ? (((uint32_t)(kk[j] >> sh) - bs) & mk) : mk;
+        uint32_t mlo, mhi;
+        match_any<8>(dg, mlo, mhi);
+        const uint32_t below = lanes_below(mlo, mhi), cnt = (uint32_t)__popc(mlo) + (uint32_t)__popc(mhi);
+        const uint32_t hs = (dg & 1u) * 16u;
+        if (below == 0) atomicAdd(&wcw[dg >> 1], cnt << hs);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");    // compiler barrier: keep the read after the add
+        const uint32_t r = ((wcw[dg >> 1] >> hs) & 0xFFFFu) - cnt + below;
+        if (j & 1) rk[j >> 1] |= r << 16; else rk[j >> 1] = r;
+    }
+    __syncthreads();
+    {
+        const uint32_t d = (uint32_t)tid;                           // (RAS_THREADS == 256: one digit per thread)
+        uint32_t c[WAVES], tot = 0;
+#pragma unroll
+        for (int q = 0; q < WAVES; q++) { c[q] = wc[q * 256 + d]; tot += c[q]; }
+        uint32_t incl = tot;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const uint32_t v = __shfl_up(incl, o, 64); if (lane >= o) incl += v; }
+        if (lane == 63) wsum[w] = incl;
+        __syncthreads();
+        uint32_t off = incl - tot;
+        for (int q = 0; q < w; q++) off += wsum[q];
+        uint32_t acc = off;
+#pragma unroll
+        for (int q = 0; q < WAVES; q++) { wc[q * 256 + d] = (uint16_t)acc; acc += c[q]; }
+        if (d == mk) tot -= RAS_TILE - nloc;                        // (the padding: the tail of digit mk's slice, not keys)
+        if (tot) {
+            RH.slice_tab[(size_t)d * RH.tab_stride + blockIdx.x] = (off << 12) | tot;
+            uint32_t* mine = RH.hist + (size_t)(blockIdx.x % HS_COPIES) * (SORT_MAX_PASSES * SORT_BINS);
+            atomicAdd(&mine[d], tot);
+            atomicAdd(&mine[SLICE_NZ_ROW * SORT_BINS + d], 1u);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < RAS_PER_THREAD; j++) {
+        const uint32_t i = w * PER_WAVE + j * 64 + lane;
+        const uint32_t dg = i < nloc ? (((uint32_t)(kk[j] >> sh) - bs) & mk) : mk;
+        stg[wc[w * 256 + dg] + ((rk[j >> 1] >> ((j & 1) * 16)) & 0xFFFFu)] = kk[j];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < RAS_PER_THREAD; q += 2) {
+        const uint32_t i = (uint32_t)q * RAS_THREADS + 2u * tid;   // 16-byte pieces, consecutive across the lanes
+        if (i + 1 < nloc) *reinterpret_cast<ulonglong2*>(out + k0 + i) = *reinterpret_cast<const ulonglong2*>(&stg[i]);
+        else if (i < nloc) out[k0 + i] = stg[i];
+    }
+}
+
+template <bool HIST, bool FUSE = false>   // HIST = false is the plain kernel; FUSE (needs HIST): the first digit pass fused in
 __global__ __launch_bounds__(RAS_THREADS, RAS_OCC) void k_rasterize(LineSource S, DevCount nc_compact, DevCount nc_segments,
                                                            const uint32_t* __restrict__ cl_idx,
                                                            const uint32_t* __restrict__ cl_start,
@@ -594,13 +682,14 @@ __global__ __launch_bounds__(RAS_THREADS, RAS_OCC) void k_rasterize(LineSource S
                                                            int band_row0, int band_row1, uint32_t* __restrict__ wg_masks,
                                                            RasHist RH) {
     __shared__ uint32_t lh[HIST ? RH_MAX_PASSES * SORT_BINS : 1];       // the sort's digit histograms of this workgroup's keys
-    __shared__ uint32_t w_start[RAS_WIN + 1];
-    __shared__ uint32_t w_order[RAS_WIN];
-    __shared__ float w_x0[RAS_WIN], w_y0[RAS_WIN], w_dx[RAS_WIN], w_dy[RAS_WIN];
-    __shared__ float w_a[RAS_WIN], w_b[RAS_WIN], w_c[RAS_WIN], w_d[RAS_WIN];
-    __shared__ double w_aab[RAS_WIN], w_bab[RAS_WIN], w_cdab[RAS_WIN], w_cdb[RAS_WIN];   // find's constants per line (find_term_k)
-    __shared__ int w_ioff[RAS_WIN];                                      // start - ioff: segment k of the line has i = k - w_ibase
-    __shared__ uint32_t red[HIST ? 7 : 5][RAS_THREADS / 64];
+    __shared__ RasLds lw;
+    uint32_t (&w_start)[RAS_WIN + 1] = lw.w.start;
+    uint32_t (&w_order)[RAS_WIN] = lw.w.order;
+    float (&w_x0)[RAS_WIN] = lw.w.x0; float (&w_y0)[RAS_WIN] = lw.w.y0; float (&w_dx)[RAS_WIN] = lw.w.dx; float (&w_dy)[RAS_WIN] = lw.w.dy;
+    float (&w_a)[RAS_WIN] = lw.w.a; float (&w_b)[RAS_WIN] = lw.w.b; float (&w_c)[RAS_WIN] = lw.w.c; float (&w_d)[RAS_WIN] = lw.w.d;
+    double (&w_aab)[RAS_WIN] = lw.w.aab; double (&w_bab)[RAS_WIN] = lw.w.bab; double (&w_cdab)[RAS_WIN] = lw.w.cdab; double (&w_cdb)[RAS_WIN] = lw.w.cdb;
+    int (&w_ioff)[RAS_WIN] = lw.w.ioff;
+    __shared__ uint32_t red[HIST ? (FUSE ? 8 : 7) : 5][RAS_THREADS / 64];   // (FUSE: row 7 = the partition's wave sums)
     const int tid = threadIdx.x;
     // the two counts and the workgroup's two table entries are independent loads: all four in flight before the first test
     // (the table is provisioned for the grid, so the entries exist even for a workgroup past the end)
@@ -724,7 +813,7 @@ __global__ __launch_bounds__(RAS_THREADS, RAS_OCC) void k_rasterize(LineSource S
             // (a digit in the key's high word — every pass of a layer-sorted frame — is one 32-bit shift, chosen by a UNIFORM branch
             //  instead of a 64-bit shift, a 32-bit one and a select per key; the runs are cut by predicated adds, no branch per key:
             //  ~6 VALU + 4 SALU per key and pass where the nested form took ~6 + 10 — 1 us per frame, `r9d`)
-            for (uint32_t p = 0; p < RH.n_passes; p++) {
+            for (uint32_t p = FUSE ? 1u : 0u; p < RH.n_passes; p++) {       // (FUSE: digit 0 is counted by the partition below)
                 const uint32_t sh = RH.shift[p], mk = RH.mask[p], bs = RH.bias[p];
                 uint32_t* h = lh + p * SORT_BINS;
                 uint32_t d[RAS_PER_THREAD];
@@ -747,12 +836,14 @@ __global__ __launch_bounds__(RAS_THREADS, RAS_OCC) void k_rasterize(LineSource S
             }
         }
     }
+    if constexpr (!FUSE) {
     // 64 contiguous bytes per thread: 16-byte stores (the tile base is a multiple of 2048 segments)
 #pragma unroll
     for (int q = 0; q < RAS_PER_THREAD; q += 2) {
         const uint32_t k = kt + q;
         if (k + 1 < k1) *reinterpret_cast<ulonglong2*>(out + k) = make_ulonglong2(vout[q], vout[q + 1]);
         else if (k < k1) out[k] = vout[q];
+    }
     }
     // block reduction of the varying-bit masks -> a few atomics per block
 #pragma unroll
@@ -775,10 +866,13 @@ __global__ __launch_bounds__(RAS_THREADS, RAS_OCC) void k_rasterize(LineSource S
         if (HIST) { red[5][w] = min_x | (max_x << 16); red[6][w] = min_y | (max_y << 16); }
     }
     __syncthreads();
+    // FUSE: the partition runs behind the mask reduction, whose values are in LDS by now — they would otherwise stay live in
+    // registers across it (and spill)
+    if constexpr (FUSE) ras_partition(vout, out, RH, lw.stg, reinterpret_cast<uint16_t*>(lh), red[7], k0, k1);
     if (HIST) {
         // flush: the non-empty bins into this workgroup's copy of the sort's histograms (a workgroup's keys cover a handful of tiles)
         uint32_t* mine = RH.hist + (size_t)(blockIdx.x % HS_COPIES) * (SORT_MAX_PASSES * SORT_BINS);
-        for (uint32_t i = tid; i < RH.n_passes * SORT_BINS; i += RAS_THREADS) {
+        for (uint32_t i = tid + (FUSE ? SORT_BINS : 0u); i < RH.n_passes * SORT_BINS; i += RAS_THREADS) {   // (FUSE: row 0 holds the partition's counters)
             const uint32_t v = lh[i];
             if (v) atomicAdd(&mine[i], v);
         }
@@ -851,7 +945,10 @@ void launch_rasterize(hipStream_t s, const LineSource& src, DevCount n_compact, 
     uint32_t blocks = (n_segments.bound + RAS_TILE - 1) / RAS_TILE;
     RasHist RH;
     memset(&RH, 0, sizeof RH);
-    if (hist && hist->hist)
+    if (hist && hist->hist && hist->slice_tab)
+        FORMA_LAUNCH((k_rasterize<true, true>), dim3(blocks), dim3(RAS_THREADS), 0, s, src, n_compact, n_segments, cl_idx, cl_start,
+                           block_first, out, info, band_row0, band_row1, wg_masks, *hist);
+    else if (hist && hist->hist)
         FORMA_LAUNCH(k_rasterize<true>, dim3(blocks), dim3(RAS_THREADS), 0, s, src, n_compact, n_segments, cl_idx, cl_start,
                            block_first, out, info, band_row0, band_row1, wg_masks, *hist);
     else

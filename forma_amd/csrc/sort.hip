@@ -23,6 +23,7 @@
 #include "lookback.h"
 #include "radix_rank.h"
 #include <string.h>
+#include <algorithm>
 #include <hip/hip_ext.h>
 
 #ifndef OS_THREADS
@@ -234,6 +235,87 @@ __global__ __launch_bounds__(HS_THREADS) void k_sort_hist(const uint64_t* __rest
 }
 
 // ------------------------------------------------------------------------------------------------
+// the first digit pass fused into the rasterizer (SliceSrc): the table of the (digit, block) slices -> the digit-major list
+// of the non-empty ones, and the slice that holds the first key of every tile of the next pass.  One workgroup per digit
+// reads its row of the table (a 4K frame: 6 720 words, one round); where the digit starts in the logical stream and in the
+// list are exclusive sums over the counts the rasterizer added up (rows 0 and SLICE_NZ_ROW of the histogram copies).
+// ------------------------------------------------------------------------------------------------
+#define SS_THREADS 256
+#define SS_PER     32
+__device__ __forceinline__ void ss_scan2(uint32_t& a, uint32_t& b, uint32_t& ta, uint32_t& tb, uint32_t (*lds)[SS_THREADS / 64]) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t ia = a, ib = b;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t va = __shfl_up(ia, o, 64), vb = __shfl_up(ib, o, 64);
+        if (lane >= o) { ia += va; ib += vb; }
+    }
+    __syncthreads();                                                    // (the previous call's readers are done)
+    if (lane == 63) { lds[0][w] = ia; lds[1][w] = ib; }
+    __syncthreads();
+    uint32_t ba = 0, bb = 0;
+    ta = 0; tb = 0;
+#pragma unroll
+    for (int q = 0; q < SS_THREADS / 64; q++) {
+        if (q < w) { ba += lds[0][q]; bb += lds[1][q]; }
+        ta += lds[0][q]; tb += lds[1][q];
+    }
+    a = ba + ia - a; b = bb + ib - b;
+}
+__global__ __launch_bounds__(SS_THREADS) void k_slice_scan(const uint32_t* __restrict__ hist, SliceSrc S, uint32_t tile,
+                                                           FrameInfo* __restrict__ info) {
+    __shared__ uint32_t s_red[2][SS_THREADS / 64];
+    __shared__ uint32_t s_base[2];
+    const int tid = threadIdx.x;
+    const uint32_t d = blockIdx.x;
+    uint32_t cnt = 0, nz = 0, n = 0, nsl = 0;
+#pragma unroll
+    for (int c = 0; c < HS_COPIES; c++) {
+        const uint32_t* h = hist + (size_t)c * (SORT_MAX_PASSES * SORT_BINS);
+        cnt += h[tid]; nz += h[SLICE_NZ_ROW * SORT_BINS + tid];
+    }
+    ss_scan2(cnt, nz, n, nsl, s_red);
+    if ((uint32_t)tid == d) { s_base[0] = cnt; s_base[1] = nz; }
+    __syncthreads();
+    uint32_t lbase = s_base[0], sbase = s_base[1];
+    uint32_t nb = (n + RAS_TILE - 1) / RAS_TILE;
+    if (nb > S.tab_stride) nb = S.tab_stride;                           // (a multiple of four)
+    const uint32_t* row = S.tab + (size_t)d * S.tab_stride;
+    for (uint32_t b0 = 0; b0 < nb; b0 += SS_THREADS * SS_PER) {
+        // consecutive words per thread (a thread's slices are consecutive in the list), 16 bytes per load: the row is 16-byte
+        // aligned and the words between nb and the next multiple of four are zero (no block wrote them)
+        uint32_t e[SS_PER];
+        const uint32_t bt = b0 + (uint32_t)tid * SS_PER;
+        uint32_t c_sum = 0, n_sum = 0;
+#pragma unroll
+        for (int q = 0; q < SS_PER; q += 4) {
+            const uint4 v = bt + q < nb ? *reinterpret_cast<const uint4*>(row + bt + q) : make_uint4(0u, 0u, 0u, 0u);
+            e[q] = v.x; e[q + 1] = v.y; e[q + 2] = v.z; e[q + 3] = v.w;
+        }
+#pragma unroll
+        for (int q = 0; q < SS_PER; q++) { c_sum += e[q] & 0xFFFu; n_sum += e[q] ? 1u : 0u; }
+        uint32_t rc, rn;
+        ss_scan2(c_sum, n_sum, rc, rn, s_red);
+        uint32_t L = lbase + c_sum, si = sbase + n_sum;
+#pragma unroll
+        for (int q = 0; q < SS_PER; q++) {
+            if (!e[q]) continue;
+            const uint32_t c = e[q] & 0xFFFu, phys = (bt + q) * RAS_TILE + (e[q] >> 12);
+            if (si < S.ent_cap) S.ent[si] = make_uint2(L, phys - L);
+            for (uint32_t t = (L + tile - 1) / tile; t * tile < L + c && t < S.first_cap; t++) S.first[t] = si;
+            L += c; si++;
+        }
+        lbase += rc; sbase += rn;
+    }
+    if (d == gridDim.x - 1 && tid == 0) {                              // sentinels: behind the last slice, behind the last tile
+        if (nsl < S.ent_cap) S.ent[nsl] = make_uint2(n, 0u);
+        const uint32_t nt = (n + tile - 1) / tile;
+        if (nt < S.first_cap) S.first[nt] = nsl;
+        info->n_slices = nsl;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // one digit pass
 // ------------------------------------------------------------------------------------------------
 // The barriers of k_onesweep's tile loop.  An LDS-only barrier (s_waitcnt lgkmcnt(0) + s_barrier, -DOS_LDS_BARRIER) that lets the
@@ -332,13 +414,17 @@ __device__ __forceinline__ uint32_t key_digit(uint64_t key, int shift, uint32_t 
     return ((uint32_t)(key >> shift) - bias) & dmask;
 }
 
-template <int BITS, bool CHUNKED, bool HI, int KPT_ = 0>
+// SL: the input is the rasterizer's digit-0-partitioned stream (SliceSrc), read in logical order: a tile stages the list entries of
+// the slices it overlaps in the (still unused) key staging area, a lane finds its first key's slice by a binary search and walks
+// forward from there, key l is at l + (physical - logical) of its slice.
+template <int BITS, bool CHUNKED, bool HI, int KPT_ = 0, bool SL = false>
 __global__ __launch_bounds__(OS_THREADS, 4) void k_onesweep(const uint64_t* __restrict__ in, uint64_t* __restrict__ out,
                                                          DevCount nc, int shift, uint32_t dmask, uint32_t bias,
                                                          const uint32_t* __restrict__ ghist /* this pass, SORT_BINS per copy */,
                                                          uint32_t* __restrict__ status /* [ntiles][RADIX] */,
                                                          uint32_t* __restrict__ ticket, uint32_t* __restrict__ err,
-                                                         ChunkedSrc C /* first pass of a chunked stream, else n_chunks = 0 */) {
+                                                         ChunkedSrc C /* first pass of a chunked stream, else n_chunks = 0 */,
+                                                         SliceSrc SS /* SL only */) {
     constexpr int RADIX = 1 << BITS;
     constexpr int KPT = KPT_ ? KPT_ : os_kpt(BITS), TILE = OS_THREADS * KPT;  // keys per lane, keys per tile
     static_assert(KPT % 2 == 0, "the 16-bit ranks of a lane are packed two per register");
@@ -351,8 +437,17 @@ __global__ __launch_bounds__(OS_THREADS, 4) void k_onesweep(const uint64_t* __re
     __shared__ uint32_t s_gdelta[RADIX];
     __shared__ uint32_t s_scan[16];
     __shared__ uint32_t s_tile;
+    __shared__ uint32_t s_sl[2];                            // SL: first list entry of s_tile's slices, number of entries
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const uint32_t ntiles = (n + TILE - 1) / TILE;
+    // SL: what the next tile's slices are, read by the thread that took its ticket
+    auto slice_range = [&](uint32_t t) {
+        if (!SL || t >= ntiles) return;
+        uint32_t s0 = SS.first[t], s1 = SS.first[t + 1];
+        s0 = min(s0, SS.ent_cap - 1u);
+        s1 = min(max(s1, s0), SS.ent_cap - 1u);
+        s_sl[0] = s0; s_sl[1] = min(s1 - s0 + 1u, (uint32_t)TILE);
+    };
 
     // a wave clears its own counters: here once, then right after it has staged a tile's keys (nobody else reads a wave's
     // row between the barrier in front of the staging and the one behind the look-back) — the tile loop has no clearing
@@ -373,7 +468,7 @@ __global__ __launch_bounds__(OS_THREADS, 4) void k_onesweep(const uint64_t* __re
 #ifdef SORT_PROF
     unsigned long long sp_t = __builtin_readcyclecounter();
 #endif
-    if (tid == 0) s_tile = atomicAdd(ticket, 1u);
+    if (tid == 0) { const uint32_t t = atomicAdd(ticket, 1u); s_tile = t; slice_range(t); }
     lds_barrier();
     while (true) {
         SP_STAMP(7);                                        // scatter + end barrier (and the prologue, once)
@@ -391,10 +486,34 @@ __global__ __launch_bounds__(OS_THREADS, 4) void k_onesweep(const uint64_t* __re
         // what pads the stream's last tile must land behind every real key of the tile: the LAST digit — with a biased digit
         // that is not the all-ones key ((~0 >> shift) - bias lands in the middle of the bins)
         const uint64_t pad = (uint64_t)(dmask + bias) << shift;
+        if (SL) {
+            const uint32_t s0 = s_sl[0], ns = s_sl[1];
+            for (uint32_t i = tid; i < ns; i += OS_THREADS) {
+                const uint2 e = SS.ent[s0 + i];
+                staged[i] = (uint64_t)e.x | ((uint64_t)e.y << 32);
+            }
+            lds_barrier();
+            uint32_t a = 0, b = ns;                         // last entry whose first logical index <= this lane's first key
+            {
+                const uint32_t l0 = wbase + lane;
+                while (b - a > 1) {
+                    const uint32_t mid = (a + b) >> 1;
+                    if ((uint32_t)staged[mid] <= l0) a = mid; else b = mid;
+                }
+            }
+            uint64_t e = staged[a], enext = a + 1 < ns ? staged[a + 1] : ~0ull;
+#pragma unroll
+            for (int j = 0; j < KPT; j++) {
+                const uint32_t idx = wbase + j * 64 + lane;
+                while ((uint32_t)enext <= idx && a + 1 < ns) { a++; e = enext; enext = a + 1 < ns ? staged[a + 1] : ~0ull; }
+                keys[j] = idx < n ? in[min(idx + (uint32_t)(e >> 32), n - 1u)] : pad;
+            }
+        } else {
 #pragma unroll
         for (int j = 0; j < KPT; j++) {
             uint32_t idx = wbase + j * 64 + lane;
             keys[j] = idx < n ? in[chunked ? chunk_phys(M, idx) : idx] : pad;      // padding: last digit, last in stream order, never written
+        }
         }
 #ifdef SORT_PROF
         if (keys[KPT - 1] == 0x123456789ull) atomicAdd(&g_sort_prof[14], 1ull);      // forces the loads to have landed
@@ -485,7 +604,8 @@ __global__ __launch_bounds__(OS_THREADS, 4) void k_onesweep(const uint64_t* __re
         lds_barrier();
         SP_STAMP(5);                                        // look-back + barrier
         // the next ticket's round trip (~1 us) runs under the scatter; every thread read s_tile barriers ago
-        if (tid == OS_THREADS - 1) s_tile = atomicAdd(ticket, 1u);
+        uint32_t next_tile = 0;
+        if (tid == OS_THREADS - 1) { next_tile = atomicAdd(ticket, 1u); s_tile = next_tile; }
         // ---- coalesced stores: every digit run leaves the CU as one contiguous piece --------------------------------
         const uint32_t nvalid = min((uint32_t)TILE, n - bbase);
         // (the compiler otherwise hoists the sixteen `j * 1024 + tid` out of the tile loop and, at the register cap, SPILLS them:
@@ -498,9 +618,11 @@ __global__ __launch_bounds__(OS_THREADS, 4) void k_onesweep(const uint64_t* __re
             if (i < nvalid) {
                 uint64_t key = staged[i];
                 uint32_t dg = key_digit<HI>(key, shift, dmask, bias);
-                out[i + s_gdelta[dg]] = key;
+                const uint32_t pos = i + s_gdelta[dg];
+                if (!SL || pos < n) out[pos] = key;         // (SL: a slice list that disagreed with the histograms stays in bounds)
             }
         }
+        if (SL && tid == OS_THREADS - 1) slice_range(next_tile);     // (behind the stores: the ticket has long returned)
         lds_barrier();
     }
 }
@@ -592,10 +714,24 @@ RasHist make_ras_hist(const SortPlan& plan, uint32_t* sort_scratch) {
     return R;
 }
 
+// [tab: 256 x stride] [first: the tiles of the smallest pass tile + 3] [ent: 2 x (non-empty slices + sentinel)]
+static inline size_t slice_stride(size_t n) { return ((n + RAS_TILE - 1) / RAS_TILE + 4) & ~(size_t)3; }
+static inline size_t slice_first_words(size_t n) { return (n + os_tile_min(n) - 1) / os_tile_min(n) + 3; }
+static inline size_t slice_ent_cap(size_t n) { return std::min(n, (size_t)256 * slice_stride(n)) + 1; }
+size_t slice_tab_words(size_t n) { return (size_t)256 * slice_stride(n); }
+size_t slice_scratch_words(size_t n) { return slice_tab_words(n) + ((slice_first_words(n) + 1) & ~(size_t)1) + 2 * slice_ent_cap(n); }
+SliceSrc make_slice_src(uint32_t* scratch, size_t n) {
+    SliceSrc S;
+    S.tab = scratch; S.tab_stride = (uint32_t)slice_stride(n);
+    S.first = scratch + slice_tab_words(n); S.first_cap = (uint32_t)slice_first_words(n);
+    S.ent = reinterpret_cast<uint2*>(S.first + ((slice_first_words(n) + 1) & ~(size_t)1)); S.ent_cap = (uint32_t)slice_ent_cap(n);
+    return S;
+}
+
 const uint64_t* launch_radix_sort(hipStream_t s, const uint64_t* in, uint64_t* a, uint64_t* b, DevCount nc,
                                   const SortPlan& plan, int digit_bits, uint32_t* scratch, uint32_t* err,
                                   const ChunkedSrc* chunked, FrameInfo* info,
-                                  bool scratch_is_zero, bool hist_ready, uint32_t max_workgroups) {
+                                  bool scratch_is_zero, bool hist_ready, uint32_t max_workgroups, const SliceSrc* sliced) {
     const size_t n = nc.bound;                        // provisioning (grid, scratch); the kernels use the device count
     if (n <= 1 || plan.n_passes == 0) return in;
     const uint32_t ntiles = (uint32_t)((n + os_tile_min(n) - 1) / os_tile_min(n));     // (row stride of the status words: sort_zero_words)
@@ -616,7 +752,12 @@ const uint64_t* launch_radix_sort(hipStream_t s, const uint64_t* in, uint64_t* a
     if (max_workgroups && max_workgroups < cap) cap = max_workgroups;   // (frames in flight: leave CUs to the other frames' kernels)
     const uint64_t* src = in;
     uint64_t* dst = a;
-    for (int p = 0; p < P; p++) {
+    // the fused first pass: the rasterizer wrote `in` partitioned by digit 0, the next pass reads it through the slice list
+    const bool sl = sliced && hist_ready && scratch_is_zero && !chunked && P >= 2 && plan.mask[0] <= 255u && digit_bits != 4;
+    SliceSrc S0;
+    memset(&S0, 0, sizeof S0);
+    const SliceSrc SS = sl ? *sliced : S0;
+    for (int p = sl ? 1 : 0; p < P; p++) {
         uint32_t* st = status + (size_t)p * ntiles * SORT_BINS;
         const bool ch = p == 0 && C.n_chunks > 1;                      // only the first pass reads the received buckets in place
         const bool hi = plan.shift[p] >= 32;
@@ -625,8 +766,12 @@ const uint64_t* launch_radix_sort(hipStream_t s, const uint64_t* in, uint64_t* a
         const uint32_t tile = (uint32_t)OS_THREADS * (uint32_t)(small_kpt ? small_kpt : os_kpt(bits));
         const uint32_t ptiles = (uint32_t)((n + tile - 1) / tile);
         const uint32_t grid = ptiles < cap ? ptiles : cap;
-#define OS_LAUNCH(B, CH, HI_, K_) FORMA_LAUNCH((k_onesweep<B, CH, HI_, K_>), dim3(grid), dim3(OS_THREADS), 0, s, src, dst, nc, \
-                                           plan.shift[p], plan.mask[p], plan.bias[p], (const uint32_t*)(hist + p * SORT_BINS), st, tickets + p, err, ch ? C : C0)
+        const bool rd = sl && p == 1;                                   // reads the rasterizer's slices
+        if (rd) FORMA_LAUNCH(k_slice_scan, dim3(plan.mask[0] + 1u), dim3(SS_THREADS), 0, s, (const uint32_t*)hist, SS, tile, info);
+#define OS_LAUNCH_(B, CH, HI_, K_, SL_) FORMA_LAUNCH((k_onesweep<B, CH, HI_, K_, SL_>), dim3(grid), dim3(OS_THREADS), 0, s, src, dst, nc, \
+                                           plan.shift[p], plan.mask[p], plan.bias[p], (const uint32_t*)(hist + p * SORT_BINS), st, tickets + p, err, ch ? C : C0, \
+                                           rd ? SS : S0)
+#define OS_LAUNCH(B, CH, HI_, K_) do { if (rd) OS_LAUNCH_(B, false, HI_, K_, true); else OS_LAUNCH_(B, CH, HI_, K_, false); } while (0)
 #define OS_LAUNCH_K(B, K_) do { if (ch) { if (hi) OS_LAUNCH(B, true, true, K_); else OS_LAUNCH(B, true, false, K_); } \
                                 else { if (hi) OS_LAUNCH(B, false, true, K_); else OS_LAUNCH(B, false, false, K_); } } while (0)
 #ifdef OS_FORCE_KPT
@@ -640,6 +785,7 @@ const uint64_t* launch_radix_sort(hipStream_t s, const uint64_t* in, uint64_t* a
 #undef OS_LAUNCH_B
 #undef OS_LAUNCH_K
 #undef OS_LAUNCH
+#undef OS_LAUNCH_
         src = dst;
         dst = (dst == a) ? b : a;
     }

@@ -88,6 +88,7 @@ SYMBOLS = {
     "forma_hip_paint": (_i, [_vp, _vp, _sz, _vp, _u32, _u32, _sz, _vp, _vp, _vp]),
     "forma_hip_render": (_i, [_vp, _vp, _u32, _u32, _sz, _vp, _vp, _vp, _i, _vp]),
     "forma_hip_render_enqueue": (_i, [_vp, _vp, _u32, _u32, _sz, _vp, _vp, _vp]),
+    "forma_hip_render_device": (_i, [_vp, _vp, _u32, _u32, _u32, _sz, _vp, _vp, _vp, _i, _vp, _vp]),
     "forma_hip_register_buffer": (_i, [_vp, _vp, _sz]),
     "forma_hip_unregister_buffer": (_i, [_vp, _vp]),
     "forma_hip_cache_clear": (_i, [_vp, _i]),

@@ -784,16 +784,8 @@ class Renderer:
         W, H = lay.width(), lay.height()
         if W > MAX_WIDTH or H > MAX_HEIGHT:
             raise FormaError(-1, "canvas exceeds MAX_WIDTH x MAX_HEIGHT")
-        composition.compact_geom()                            # renderer.rs:113
-        sh = composition._shared
-        if self._geom_owner is not sh or self._geom_version != sh.geometry_version:
-            self._upload_geometry(composition)
         cache_id = buffer.layer_cache.id if buffer.layer_cache else None
-        # the layer / style / unchanged tables stay resident: they are rebuilt only when something they depend on changed
-        key = (sh, sh.table_version, sh.unchanged_version if cache_id is not None else -1, cache_id)
-        if key != self._tables_key:
-            self._upload_tables(composition, cache_id)
-            self._tables_key = key
+        sh = self._upload_scene(composition, cache_id)
         dst = buffer.buffer
         rect = None if crop is None else (crop.horizontal.start, crop.horizontal.stop, crop.vertical.start, crop.vertical.stop)
         clear = (clear_color.r, clear_color.g, clear_color.b, clear_color.a)
@@ -826,6 +818,21 @@ class Renderer:
                 type(lay).write(slices[int(t) * spt: (int(t) + 1) * spt], buffer.flusher, TileFill.Full(tile.reshape(256, 4)))
         if timings:
             self.last_timings = out[1] if isinstance(out, tuple) else out
+        self._mark_unchanged(composition, sh, cache_id)
+
+    def _upload_scene(self, composition: Composition, cache_id: Optional[int]):
+        composition.compact_geom()                            # renderer.rs:113
+        sh = composition._shared
+        if self._geom_owner is not sh or self._geom_version != sh.geometry_version:
+            self._upload_geometry(composition)
+        # the layer / style / unchanged tables stay resident: they are rebuilt only when something they depend on changed
+        key = (sh, sh.table_version, sh.unchanged_version if cache_id is not None else -1, cache_id)
+        if key != self._tables_key:
+            self._upload_tables(composition, cache_id)
+            self._tables_key = key
+        return sh
+
+    def _mark_unchanged(self, composition: Composition, sh, cache_id: Optional[int]):
         if cache_id is not None:                              # renderer.rs:217-223
             mkey = (sh, sh.table_version, cache_id)
             if mkey != self._marked_key:                      # (nothing to do when this exact state was marked already)
@@ -839,3 +846,38 @@ class Renderer:
                 if changed:
                     sh.unchanged_version += 1
                 self._marked_key = mkey
+
+    def render_to_device(self, composition: Composition, out, channels=RGBA, clear_color: Color = Color(1, 1, 1, 1),
+                         crop: Optional[Rect] = None, layer_cache: Optional[BufferLayerCache] = None, timings: bool = False):
+        """The GPU backend's `Renderer::render_to_texture` (reference gpu/renderer/mod.rs:462-520): paint straight into `out`, a
+        torch tensor [H, W, 4] on the renderer's device — uint8: the sRGB bytes `render` writes; float16: the painter's linear
+        colour (forma_hip_render_device).  Rows may be padded (`out` may be a view into a wider tensor): the pitch is
+        `out.stride(0)`.  The frame waits for the work already enqueued on torch's current stream.  With several frames in
+        flight and no cache / timings the frame is enqueued: `out` is complete after `sync()` of the renderer's context."""
+        import torch
+        if not isinstance(out, torch.Tensor):
+            raise ValueError("out must be a torch.Tensor")
+        fmt = {torch.uint8: "srgb8", torch.float16: "linear_f16"}.get(out.dtype)
+        if fmt is None:
+            raise ValueError(f"out must be uint8 (sRGB8) or float16 (linear), not {out.dtype}")
+        if out.dim() != 3 or out.shape[2] != 4:
+            raise ValueError(f"out must have shape [H, W, 4], not {list(out.shape)}")
+        dev = torch.device("cuda", self._ctx.device)
+        if out.device != dev:
+            raise ValueError(f"out must live on {dev} (the renderer's device), not {out.device}")
+        if out.stride(2) != 1 or out.stride(1) != 4:
+            raise ValueError("out must have contiguous pixels: stride(2) == 1 and stride(1) == 4")
+        H, W = int(out.shape[0]), int(out.shape[1])
+        if W > MAX_WIDTH or H > MAX_HEIGHT:
+            raise FormaError(-1, "canvas exceeds MAX_WIDTH x MAX_HEIGHT")
+        cache_id = layer_cache.id if layer_cache else None
+        sh = self._upload_scene(composition, cache_id)
+        rect = None if crop is None else (crop.horizontal.start, crop.horizontal.stop, crop.vertical.start, crop.vertical.stop)
+        clear = (clear_color.r, clear_color.g, clear_color.b, clear_color.a)
+        t = self._ctx.render_device(out.data_ptr(), fmt, W, H, out.stride(0) * out.element_size(), channels=channels, clear=clear,
+                                    crop=rect, cache_id=-1 if cache_id is None else cache_id,
+                                    wait_stream=torch.cuda.current_stream(dev).cuda_stream, timings=timings)
+        if timings:
+            self.last_timings = t
+        self._mark_unchanged(composition, sh, cache_id)
+        return out

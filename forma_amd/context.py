@@ -194,6 +194,23 @@ class Context:
         self._check(self._L.forma_hip_render_enqueue(self._h, _p(dst), width, height, stride, _p(ch), _p(cl),
                                                      None if rect is None else C.addressof(rect)))
 
+    FORMATS = {"srgb8": 0, "linear_f16": 1}
+
+    def render_device(self, ptr, fmt, width, height, stride, channels=(0, 1, 2, 3), clear=(1, 1, 1, 0), crop=None,
+                      cache_id=-1, wait_stream=None, timings=False):
+        """forma_hip_render_device: paint into caller DEVICE memory at address `ptr` (an int) of this context's GPU, pitch `stride`
+        bytes, format 'srgb8' / 'linear_f16' (or 0 / 1); `wait_stream`: a hipStream_t handle (int) whose earlier work the frame
+        waits for on the device (None: the null stream).  Returns the timings dict when asked for, else None."""
+        f = self.FORMATS[fmt] if isinstance(fmt, str) else int(fmt)
+        ch = np.asarray(channels, np.uint8); cl = np.asarray(clear, np.float32)
+        rect = None if crop is None else RectT(*crop)
+        t = TimingsT() if timings else None
+        self._check(self._L.forma_hip_render_device(self._h, C.c_void_p(int(ptr)), f, width, height, stride, _p(ch), _p(cl),
+                                                    None if rect is None else C.addressof(rect), cache_id,
+                                                    C.c_void_p(int(wait_stream)) if wait_stream else None,
+                                                    None if t is None else C.addressof(t)))
+        return t.as_dict() if timings else None
+
     def register_buffer(self, arr):
         """forma_hip_register_buffer: page-lock a numpy buffer the renderer writes often (keep it alive until unregister / close)"""
         self._check(self._L.forma_hip_register_buffer(self._h, _p(arr), arr.nbytes))

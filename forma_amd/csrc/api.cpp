@@ -406,6 +406,11 @@ struct PaintArgs {
     const float* clear;
     const forma_rect_t* crop;
     int cache_id = -1;
+    // forma_hip_render_device: the painters write straight into the caller's device memory (pitch in bytes, FORMA_FORMAT_*);
+    // nullptr: into the context's scratch image or the cache's own image, as RGBA8
+    uint8_t* target = nullptr;
+    size_t target_pitch = 0;
+    uint32_t fmt = FORMA_FORMAT_SRGB8;
 };
 
 // A synchronous frame into caller memory is PCIe from the painter's last tile on: 33 MB of a 4K image take ~600 us behind ~450 us
@@ -451,20 +456,25 @@ int run_paint(forma_hip_ctx* ctx, DevCount nc, const PaintArgs& a, bool timing, 
     TileCacheArgs tc{nullptr, nullptr};
     uint32_t clear_unchanged = 0;
     ctx->cur_cache = a.cache_id;
+    ctx->image_external = a.target != nullptr;
     if (a.cache_id >= 0) {
         forma_hip_ctx::TileCache& c = ctx->caches[a.cache_id];
         HIPCHECK(c.tiles.ensure((size_t)T * 8));
-        HIPCHECK(c.image.ensure((size_t)a.width * a.height * 4));
+        if (!a.target) HIPCHECK(c.image.ensure((size_t)a.width * a.height * 4));
         HIPCHECK(ctx->cache_written.ensure((size_t)T));
-        if (c.w != a.width || c.h != a.height) {                       // renderer.rs:94-111: new size -> cache cleared
+        // renderer.rs:94-111: new size -> cache cleared; so is a new target (the tiles it skips must show what IT painted last)
+        if (c.w != a.width || c.h != a.height || c.target != a.target || c.target_pitch != a.target_pitch) {
             c.w = a.width; c.h = a.height; c.has_clear = false;
+            c.target = a.target; c.target_pitch = a.target_pitch;
             HIPCHECK(hipMemsetAsync(c.tiles.p, 0, (size_t)T * 8, ctx->stream));
-            HIPCHECK(hipMemsetAsync(c.image.p, 0, (size_t)a.width * a.height * 4, ctx->stream));
+            if (!a.target) HIPCHECK(hipMemsetAsync(c.image.p, 0, (size_t)a.width * a.height * 4, ctx->stream));
         }
         HIPCHECK(hipMemsetAsync(ctx->cache_written.p, 0, (size_t)T, ctx->stream));
         tc.tiles = c.tiles.as<uint2>(); tc.written = ctx->cache_written.as<uint8_t>();
         clear_unchanged = c.has_clear && memcmp(c.clear, a.clear, sizeof c.clear) == 0 ? 1u : 0u;
-        ctx->cur_image = c.image.as<uint8_t>();
+        ctx->cur_image = a.target ? a.target : c.image.as<uint8_t>();
+    } else if (a.target) {
+        ctx->cur_image = a.target;
     } else {
         HIPCHECK(ctx->image.ensure((size_t)a.width * a.height * 4));
         ctx->cur_image = ctx->image.as<uint8_t>();
@@ -706,7 +716,7 @@ int run_paint(forma_hip_ctx* ctx, DevCount nc, const PaintArgs& a, bool timing, 
         for (int i = 0; i < 4; i++) if (ch[i] == FORMA_CH_ALPHA) ch[i] = FORMA_CH_ONE;
     P.channels = (uint32_t)ch[0] | ((uint32_t)ch[1] << 8) | ((uint32_t)ch[2] << 16) | ((uint32_t)ch[3] << 24);
     for (int i = 0; i < 4; i++) P.clear[i] = a.clear[i];
-    P.stride_px = a.width; P.scene_has_clips = ctx->scene_has_clips ? 1u : 0u; P.scene_simple = ctx->scene_simple ? 1u : 0u; P.n_orders = (uint32_t)ctx->n_orders; P.n_words = (uint32_t)ctx->n_words;
+    P.stride_px = a.target ? (uint32_t)(a.target_pitch / (a.fmt == FORMA_FORMAT_LINEAR_F16 ? 8u : 4u)) : a.width; P.scene_has_clips = ctx->scene_has_clips ? 1u : 0u; P.scene_simple = ctx->scene_simple ? 1u : 0u; P.n_orders = (uint32_t)ctx->n_orders; P.n_words = (uint32_t)ctx->n_words;
     P.clear_unchanged = clear_unchanged;
     P.n_slices = jc.bound > 0 ? n_slices : 1u;             // (no runs: the carry pre-pass did not run, the zeroed tables say "no spans")
     P.n_groups = n_groups;
@@ -797,7 +807,7 @@ int run_paint(forma_hip_ctx* ctx, DevCount nc, const PaintArgs& a, bool timing, 
                          ctx->style_off.as<uint32_t>(),
                          ctx->style_words.as<uint32_t>(), ctx->images.as<forma_image_t>(), ctx->texels.as<uint16_t>(),
                          ctx->cur_image, tc, dinfo, paint_overflow, overflow_list, over2_n, over2_list, false, groups,
-                         strips, quads, mid_n, mid_list, ctx->n_cus);
+                         strips, quads, mid_n, mid_list, ctx->n_cus, a.fmt);
             HIPCHECK(hipEventRecord(ctx->split_ev[k], ctx->stream));
         }
         ctx->split_n = split_n;
@@ -807,12 +817,12 @@ int run_paint(forma_hip_ctx* ctx, DevCount nc, const PaintArgs& a, bool timing, 
                  ctx->style_off.as<uint32_t>(),
                  ctx->style_words.as<uint32_t>(), ctx->images.as<forma_image_t>(), ctx->texels.as<uint16_t>(),
                  ctx->cur_image, tc, dinfo, paint_overflow, overflow_list, over2_n, over2_list, launch_deep, groups,
-                 strips, quads, mid_n, mid_list, ctx->n_cus);
+                 strips, quads, mid_n, mid_list, ctx->n_cus, a.fmt);
     stage_end(ctx, ST_PAINT, timing);
     ctx->last_runs = J; ctx->last_entries = 0;
     HIPCHECK(hipGetLastError());
     // what a later launch_paint_huge needs (tiles deeper than the painter's LDS lists: finish_paint)
-    ctx->huge = forma_hip_ctx::HugeArgs{P, jc, tc, tile_first_run, row_span_lo, row_span_cnt, over2_n, over2_list, T};
+    ctx->huge = forma_hip_ctx::HugeArgs{P, jc, tc, tile_first_run, row_span_lo, row_span_cnt, over2_n, over2_list, T, a.fmt};
     return FORMA_OK;
 }
 
@@ -845,7 +855,7 @@ int finish_paint(forma_hip_ctx* ctx) {
                       ctx->span_key.as<uint64_t>(), ctx->span_cov.as<uint4>(), ctx->layer_col.as<uint4>(), ctx->style_off.as<uint32_t>(),
                       ctx->style_words.as<uint32_t>(), ctx->images.as<forma_image_t>(), ctx->texels.as<uint16_t>(), ctx->cur_image, h.tc,
                       ctx->info.as<FrameInfo>(), h.over2_list, n, ctx->huge_offs.as<uint64_t>(), ctx->huge_key.as<uint64_t>(),
-                      ctx->huge_tmp.as<uint64_t>(), ctx->huge_flag.as<uint32_t>());
+                      ctx->huge_tmp.as<uint64_t>(), ctx->huge_flag.as<uint32_t>(), h.fmt);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(ctx->stream));           // (`offs` is host memory of this call)
     // what the huge pass itself reported lands in the frame's host copy: finish_frame looks at fresh error bits
@@ -910,6 +920,10 @@ int copy_image_out(forma_hip_ctx* ctx, uint8_t* dst, size_t stride, bool timing,
     ctx->last_written = 0;
     ctx->lw_valid = true; ctx->lw_tiles_w = tiles_w; ctx->lw_tiles_h = tiles_h; ctx->lw_cache = a.cache_id >= 0; ctx->lw_flags_on_host = false;
     ctx->lw_tx0 = tx0; ctx->lw_tx1 = std::max(tx0, tx1); ctx->lw_ty0 = ty0; ctx->lw_ty1 = std::max(ty0, ty1);
+    if (a.target) {                                        // (a device target: the painters wrote into it, nothing is copied)
+        if (tx0 < tx1 && ty0 < ty1 && a.cache_id < 0) ctx->last_written = (tx1 - tx0) * (ty1 - ty0);
+        return FORMA_OK;
+    }
     if (!dst) return FORMA_OK;
     if (tx0 >= tx1 || ty0 >= ty1) return FORMA_OK;
     ctx->last_written = (tx1 - tx0) * (ty1 - ty0);
@@ -1184,6 +1198,7 @@ void forma_hip_destroy(forma_hip_ctx* ctx) {
         for (int k = 0; k < forma_hip_ctx::SPLIT_MAX; k++) if (ctx->split_ev[k]) (void)hipEventDestroy(ctx->split_ev[k]);
         (void)hipStreamDestroy(ctx->copy_stream);
     }
+    if (ctx->wait_ev) (void)hipEventDestroy(ctx->wait_ev);
     (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -1634,7 +1649,7 @@ int settle_slot(forma_hip_ctx* sl) {
     forma_hip_ctx* ctx = sl;
     HIPCHECK(hipSetDevice(sl->device));
     const forma_hip_ctx::Deferred& d = sl->def;
-    PaintArgs a{d.width, d.height, d.channels, d.clear, d.has_crop ? &d.crop : nullptr, -1};
+    PaintArgs a{d.width, d.height, d.channels, d.clear, d.has_crop ? &d.crop : nullptr, -1, d.target, d.target_pitch, d.fmt};
     int rc = complete_async_frame(sl, a, d.dst, d.stride, false, nullptr, d.bN, d.bJ);
     if (rc == FORMA_RETRY) rc = render_sync(sl, a, d.dst, d.stride, false, nullptr);
     return rc;
@@ -1682,16 +1697,27 @@ void invalidate_counts(forma_hip_ctx* o) {                 // new geometry / ban
 
 extern "C" {
 
+// the caller's device target of forma_hip_render_device (target == nullptr: a frame into the scratch image / host memory)
+struct DeviceTarget { uint8_t* target = nullptr; size_t pitch = 0; uint32_t fmt = FORMA_FORMAT_SRGB8; hipStream_t wait = nullptr; };
+
+// forma_hip_render_device's wait_stream: the frame's stream waits (on the device) for what was enqueued there before the call
+static int wait_for_caller(forma_hip_ctx* ctx, hipStream_t frame_stream, hipStream_t wait) {
+    if (!ctx->wait_ev) HIPCHECK(hipEventCreateWithFlags(&ctx->wait_ev, hipEventDisableTiming));
+    HIPCHECK(hipEventRecord(ctx->wait_ev, wait));
+    HIPCHECK(hipStreamWaitEvent(frame_stream, ctx->wait_ev, 0));
+    return FORMA_OK;
+}
+
 static int render_impl(forma_hip_ctx* ctx, uint8_t* dst, uint32_t width, uint32_t height, size_t stride_bytes,
                        const uint8_t channels[4], const float clear_color[4], const forma_rect_t* crop_or_null, int cache_id,
-                       forma_timings_t* timings, bool defer_dst) {
+                       forma_timings_t* timings, bool defer_dst, const DeviceTarget& dt = DeviceTarget()) {
     if (!ctx) return FORMA_E_ARG;
     int rc = check_paint_args(ctx, dst, width, height, stride_bytes, channels, clear_color);
     if (rc) return rc;
     if (cache_id >= 32) return fail(ctx, FORMA_E_ARG, "cache_id out of range");   // SmallBitSet u32, small_bit_set.rs:17-57
     if (ctx->multi) return multi_render(ctx, dst, width, height, stride_bytes, channels, clear_color, crop_or_null, cache_id, timings);
     HIPCHECK(hipSetDevice(ctx->device));
-    PaintArgs a{width, height, channels, clear_color, crop_or_null, cache_id};
+    PaintArgs a{width, height, channels, clear_color, crop_or_null, cache_id, dt.target, dt.pitch, dt.fmt};
     // Several frames in flight: a device-resident frame without a cache is ENQUEUED on the next slot and this call returns;
     // it is verified (and, if a prediction failed, re-run) when the slot is needed again or when any call needs its result.
     // Frames that write caller memory, use a buffer-layer cache (frame k + 1 reads what frame k left in it) or ask for
@@ -1708,7 +1734,9 @@ static int render_impl(forma_hip_ctx* ctx, uint8_t* dst, uint32_t width, uint32_
             d.width = width; d.height = height; memcpy(d.channels, channels, 4); memcpy(d.clear, clear_color, 16);
             d.has_crop = crop_or_null != nullptr; if (crop_or_null) d.crop = *crop_or_null;
             d.dst = dst; d.stride = stride_bytes;
-            PaintArgs as{width, height, d.channels, d.clear, d.has_crop ? &d.crop : nullptr, -1};
+            d.target = dt.target; d.target_pitch = dt.pitch; d.fmt = dt.fmt;
+            PaintArgs as{width, height, d.channels, d.clear, d.has_crop ? &d.crop : nullptr, -1, d.target, d.target_pitch, d.fmt};
+            if (dt.target && (rc = wait_for_caller(ctx, sl->stream, dt.wait))) return rc;
             sl->frame_has_dst = dst != nullptr;                   // (sort_workgroups: such a frame's digit passes keep the whole chip)
             rc = enqueue_async_frame(sl, as, false, &d.bN, &d.bJ);
             sl->frame_has_dst = false;
@@ -1720,6 +1748,7 @@ static int render_impl(forma_hip_ctx* ctx, uint8_t* dst, uint32_t width, uint32_
                 sl->image_sent = rc == FORMA_OK;
             }
         } else {
+            if (dt.target && (rc = wait_for_caller(ctx, sl->stream, dt.wait))) return rc;
             rc = render_sync(sl, a, dst, stride_bytes, false, nullptr);
         }
         if (rc && sl != ctx) memcpy(ctx->err, sl->err, sizeof ctx->err);
@@ -1727,6 +1756,7 @@ static int render_impl(forma_hip_ctx* ctx, uint8_t* dst, uint32_t width, uint32_
     }
     if ((rc = fd_drain(ctx))) return rc;
     ctx->last = ctx;
+    if (dt.target && (rc = wait_for_caller(ctx, ctx->stream, dt.wait))) return rc;
     return render_on(ctx, dst, a, stride_bytes, timings);
 }
 
@@ -1739,6 +1769,47 @@ int forma_hip_render(forma_hip_ctx* ctx, uint8_t* dst, uint32_t width, uint32_t 
 int forma_hip_render_enqueue(forma_hip_ctx* ctx, uint8_t* dst, uint32_t width, uint32_t height, size_t stride_bytes,
                              const uint8_t channels[4], const float clear_color[4], const forma_rect_t* crop_or_null) {
     return render_impl(ctx, dst, width, height, stride_bytes, channels, clear_color, crop_or_null, -1, nullptr, true);
+}
+
+// render_to_texture (reference gpu/renderer/mod.rs:462-520): the painters write straight into the caller's device memory.  The
+// frame is a dst == NULL frame in every other respect — same kernels, same slots, same speculation — with the image pointer and
+// pitch of the target and the painters' FMT; the host-memory paths (copy_image_out's copies and packing, the split bands) see
+// dst == NULL and stay away.
+int forma_hip_render_device(forma_hip_ctx* ctx, void* dst_device, uint32_t format, uint32_t width, uint32_t height,
+                            size_t stride_bytes, const uint8_t channels[4], const float clear_color[4],
+                            const forma_rect_t* crop_or_null, int cache_id, void* wait_stream, forma_timings_t* timings) {
+    if (!ctx) return FORMA_E_ARG;
+    int rc = check_paint_args(ctx, nullptr, width, height, stride_bytes, channels, clear_color);
+    if (rc) return rc;
+    if (format != FORMA_FORMAT_SRGB8 && format != FORMA_FORMAT_LINEAR_F16) return fail(ctx, FORMA_E_ARG, "unknown target format");
+    if (cache_id >= 32) return fail(ctx, FORMA_E_ARG, "cache_id out of range");
+    if (cache_id >= 0 && format != FORMA_FORMAT_SRGB8)
+        return fail(ctx, FORMA_E_ARG, "a buffer-layer cache needs an SRGB8 target (the reference's GPU renderer has none)");
+    const size_t bpp = format == FORMA_FORMAT_LINEAR_F16 ? 8 : 4;
+    if (!dst_device) return fail(ctx, FORMA_E_ARG, "null target");
+    if (stride_bytes < (size_t)width * bpp || stride_bytes % bpp || stride_bytes / bpp > 0xFFFFFFFFull)
+        return fail(ctx, FORMA_E_ARG, "stride must be at least width * bytes per pixel and a multiple of it");
+    if ((uintptr_t)dst_device % bpp) return fail(ctx, FORMA_E_ARG, "target not aligned to its pixel size");
+    if (ctx->multi) return fail(ctx, FORMA_E_STATE, "device targets are single-device (a multi-device context paints bands on several GPUs)");
+    HIPCHECK(hipSetDevice(ctx->device));
+    // device memory of THIS device, large enough for the canvas: the painters store into it without further checks
+    hipPointerAttribute_t pa;
+    const hipError_t pe = hipPointerGetAttributes(&pa, dst_device);
+    if (pe != hipSuccess) {
+        (void)hipGetLastError();                           // (an unknown pointer is an argument error, not a sticky runtime error)
+        return fail(ctx, FORMA_E_ARG, "target is not memory this HIP runtime knows (host memory, or torch loaded after this library?)");
+    }
+    if (pa.type != hipMemoryTypeDevice || pa.isManaged || pa.device != ctx->device)
+        return fail(ctx, FORMA_E_ARG, "target must be device memory of the context's device (not host, pinned, managed or another device's)");
+    hipDeviceptr_t base = nullptr; size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)dst_device) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ctx, FORMA_E_ARG, "target allocation not found");
+    }
+    const size_t need = (size_t)(height - 1) * stride_bytes + (size_t)width * bpp;
+    if ((uintptr_t)dst_device + need > (uintptr_t)base + size) return fail(ctx, FORMA_E_ARG, "target allocation smaller than the canvas");
+    DeviceTarget dt{(uint8_t*)dst_device, stride_bytes, format, (hipStream_t)wait_stream};
+    return render_impl(ctx, nullptr, width, height, stride_bytes, channels, clear_color, crop_or_null, cache_id, timings, false, dt);
 }
 
 // Caller buffers the renderer writes often (a window's frame buffer): page-locked once, the device-to-host copies into them are
@@ -1916,6 +1987,7 @@ int forma_hip_read_image(forma_hip_ctx* ctx, uint8_t* dst, size_t stride_bytes) 
     if (ctx != owner) ctx->err[0] = 0;
     struct CopyErr { forma_hip_ctx* o; forma_hip_ctx* s; ~CopyErr() { if (o != s && s->err[0]) memcpy(o->err, s->err, sizeof o->err); } } copy_err{owner, ctx};
     if (!ctx->img_w) return fail(ctx, FORMA_E_STATE, "no image on the device");
+    if (ctx->image_external) return fail(ctx, FORMA_E_STATE, "the last frame was painted into caller device memory (forma_hip_render_device)");
     if ((size_t)ctx->img_w * 4 > stride_bytes) return fail(ctx, FORMA_E_ARG, "width exceeds width stride");
     HIPCHECK(hipSetDevice(ctx->device));
     HIPCHECK(hipMemcpy2D(dst, stride_bytes, ctx->cur_image, (size_t)ctx->img_w * 4, (size_t)ctx->img_w * 4, ctx->img_h, hipMemcpyDeviceToHost));
@@ -2405,7 +2477,7 @@ forma_hip_ctx* fd_last_slot(forma_hip_ctx* ctx) { return ctx->last ? ctx->last :
 
 int fd_copy_image_rows(forma_hip_ctx* ctx, uint8_t* dst, size_t stride_bytes, uint32_t y0, uint32_t y1) {
     if (!ctx || !dst) return FORMA_E_ARG;
-    if (!ctx->img_w || !ctx->cur_image) return fail(ctx, FORMA_E_STATE, "no image on the device");
+    if (!ctx->img_w || !ctx->cur_image || ctx->image_external) return fail(ctx, FORMA_E_STATE, "no image on the device");
     y1 = std::min(y1, ctx->img_h);
     if (y0 >= y1) return FORMA_OK;
     HIPCHECK(hipSetDevice(ctx->device));

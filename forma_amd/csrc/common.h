@@ -466,7 +466,8 @@ void launch_paint(hipStream_t s, const PaintParams& p, const uint64_t* sorted, c
                   bool quads = false /* four tiles per wavefront (k_paint_quad): all-solid scenes with shallow tiles; ignored otherwise */,
                   uint32_t* mid_n = nullptr /* zeroed by launch_runs */, uint32_t* mid_list = nullptr /* {tile, entries} pairs of the tiles beyond
                                          k_paint_deep's 1024-entry tier: 2 * tiles_w * tiles_h words (both required with launch_deep) */,
-                  uint32_t n_cus = 256);
+                  uint32_t n_cus = 256,
+                  uint32_t fmt = FORMA_FORMAT_SRGB8 /* FORMA_FORMAT_*: what the painters store (image pitch: p.stride_px pixels of it) */);
 // tiles whose layer list exceeds the painter's LDS lists (info->error bit 3 after launch_paint): lists in global memory,
 // offs[i] = first entry slot of tile over2_list[2 i]; g_key holds 4 entries per slot, g_tmp / g_flag one
 void launch_paint_huge(hipStream_t s, const PaintParams& p, const uint64_t* sorted, const TileRecord* records, DevCount n_runs,
@@ -474,4 +475,5 @@ void launch_paint_huge(hipStream_t s, const PaintParams& p, const uint64_t* sort
                        const uint64_t* span_key, const uint4* span_cov, const uint4* layer_col,
                        const uint32_t* style_offsets, const uint32_t* style_words, const forma_image_t* images,
                        const uint16_t* texels, uint8_t* image, TileCacheArgs cache, FrameInfo* info, const uint32_t* over2_list,
-                       uint32_t n_tiles, const uint64_t* offs, uint64_t* g_key, uint64_t* g_tmp, uint32_t* g_flag);
+                       uint32_t n_tiles, const uint64_t* offs, uint64_t* g_key, uint64_t* g_tmp, uint32_t* g_flag,
+                       uint32_t fmt = FORMA_FORMAT_SRGB8);

@@ -107,6 +107,9 @@ struct forma_hip_ctx {
         uint32_t w = 0, h = 0;
         bool has_clear = false;
         float clear[4] = {0, 0, 0, 0};
+        // what the cache last painted into: its own image (nullptr) or a caller's device target (forma_hip_render_device) with
+        // its pitch.  A BufferLayerCache belongs to one Buffer: when the target changes, the tile state is cleared
+        const void* target = nullptr; size_t target_pitch = 0;
     };
     TileCache caches[32];
     DevBuf pack_list, pack_pix;             // cache frames: written tiles of the crop (list + count word in front), their pixels packed
@@ -130,6 +133,8 @@ struct forma_hip_ctx {
     std::vector<std::pair<void*, size_t>> registered;   // caller buffers pinned by forma_hip_register_buffer
     int cur_cache = -1;                     // cache of the frame in flight
     uint8_t* cur_image = nullptr;           // device image of the frame in flight / last frame
+    bool image_external = false;            // ... is the caller's device target (forma_hip_render_device): forma_hip_read_image refuses it
+    hipEvent_t wait_ev = nullptr;           // forma_hip_render_device's wait_stream: recorded there, waited for on the frame's stream
     // sort-plan speculation: the varying-bit mask and the layer-sortedness of a scene rarely change between frames, so
     // forma_hip_render plans the sort from the previous frame's values and verifies them when the frame is done
     bool pred_valid = false, pred_layer_sorted = false, speculated = false;
@@ -166,7 +171,7 @@ struct forma_hip_ctx {
     struct HugeArgs {
         PaintParams P; DevCount jc; TileCacheArgs tc;
         const uint32_t* tile_first_run; const uint32_t* row_span_lo; const uint32_t* row_span_cnt;
-        uint32_t* over2_n; uint32_t* over2_list; uint32_t T;
+        uint32_t* over2_n; uint32_t* over2_list; uint32_t T; uint32_t fmt;
     } huge{};
     DevBuf huge_offs, huge_key, huge_tmp, huge_flag;
     // band
@@ -190,6 +195,7 @@ struct forma_hip_ctx {
         float clear[4] = {0, 0, 0, 0};
         bool has_crop = false;
         forma_rect_t crop = {0, 0, 0, 0};
+        uint8_t* target = nullptr; size_t target_pitch = 0; uint32_t fmt = 0;   // forma_hip_render_device: the caller's device target
     } def;
     // several devices behind this context (forma_hip_create_multi): the context is then a shell, the work happens in
     // multi->kid[g] (one full context per device)

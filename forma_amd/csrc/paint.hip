@@ -1762,6 +1762,24 @@ __device__ __forceinline__ float sel_channel(uint32_t c, float r, float g, float
     switch (c) { case 0: return r; case 1: return g; case 2: return b; case 3: return a; case 4: return 0.0f; default: return 1.0f; }
 }
 
+// ---- the painters' output format (forma_hip.h FORMA_FORMAT_*): a template parameter of every painter, never a runtime branch.
+// FMT_SRGB8: 4 bytes per pixel, the encode above.  FMT_F16: 8 bytes per pixel, the painter's LINEAR colour with the channels
+// selected on floats, converted to IEEE binary16 with round-to-nearest-even and no clamp — what the reference's GPU painter
+// stores into its Rgba16Float target (gpu/painter/paint.wgsl:954, gpu/renderer/mod.rs:176-191).  A pixel is ONE 8-byte store,
+// so a wave's lanes still write contiguous runs of a row.
+#define FMT_SRGB8 0
+#define FMT_F16   1
+__device__ __forceinline__ uint32_t pack_f16x2(float lo, float hi) {
+    const _Float16 a = (_Float16)lo, b = (_Float16)hi;             // v_cvt_f16_f32: RNE in the default mode (not cvt_pkrtz: truncates)
+    return (uint32_t)__builtin_bit_cast(uint16_t, a) | ((uint32_t)__builtin_bit_cast(uint16_t, b) << 16);
+}
+__device__ __forceinline__ uint2 linear_f16x4(uint32_t channels, float r, float g, float b, float a) {
+    float s[4];
+#pragma unroll
+    for (int c = 0; c < 4; c++) s[c] = sel_channel((channels >> (8 * c)) & 0xFFu, r, g, b, a);
+    return make_uint2(pack_f16x2(s[0], s[1]), pack_f16x2(s[2], s[3]));
+}
+
 // ---- fills (cpu/painter/styling.rs:58-193), per pixel -----------------------------------------------------
 template <typename WP>
 __device__ __forceinline__ void gradient_at(WP w, uint32_t fill, uint32_t nstops, float x,
@@ -1965,6 +1983,7 @@ __device__ __forceinline__ uint32_t span_phys(const SpanListsT<NS>& L, uint32_t 
 // each).  k_paint_deep passes LDS (cap 4096); a tile that does not fit is recorded as {tile, entries} in `over2`, and
 // k_paint_huge paints it with lists in global memory sized for exactly that tile — the reference has no limit on the layers
 // of a tile (LayerWorkbench::populate_layers, layer_workbench/mod.rs:250-278) and neither has this path.
+template <int FMT>
 __device__ __forceinline__ void paint_tile(const uint32_t MAXE, const uint32_t STAGE, uint64_t* e_key, uint64_t* e_tmp, uint32_t* e_flag,
                                            const PaintParams& P, const uint32_t tile, const uint64_t* __restrict__ sorted,
                                            const TileRecord* __restrict__ records, const uint32_t n_runs_frame,
@@ -2202,11 +2221,17 @@ __device__ __forceinline__ void paint_tile(const uint32_t MAXE, const uint32_t S
             }
         }
         if (tid == 0 && ok) {                                           // to_srgb_bytes(channels.map(color.channel)) :156-162, 690
-            float sel[4];
+            if constexpr (FMT == FMT_F16) {
+                // the selected linear colour; its two words travel in b_col[0], which nobody reads until the paint loop stages
+                const uint2 v = linear_f16x4(P.channels, dst.r, dst.g, dst.b, dst.a);
+                b_col[0] = make_uint4(v.x, v.y, 0u, 0u);
+            } else {
+                float sel[4];
 #pragma unroll
-            for (int c = 0; c < 4; c++) sel[c] = sel_channel((P.channels >> (8 * c)) & 0xFFu, dst.r, dst.g, dst.b, dst.a);
-            s_solid_bytes = to_u8_x4(linear_to_srgb(sel[0])) | (to_u8_x4(linear_to_srgb(sel[1])) << 8) |
-                            (to_u8_x4(linear_to_srgb(sel[2])) << 16) | (to_u8_x4(sel[3]) << 24);
+                for (int c = 0; c < 4; c++) sel[c] = sel_channel((P.channels >> (8 * c)) & 0xFFu, dst.r, dst.g, dst.b, dst.a);
+                s_solid_bytes = to_u8_x4(linear_to_srgb(sel[0])) | (to_u8_x4(linear_to_srgb(sel[1])) << 8) |
+                                (to_u8_x4(linear_to_srgb(sel[2])) << 16) | (to_u8_x4(sel[3]) << 24);
+            }
             s_solid = 1;
         }
     }
@@ -2216,6 +2241,11 @@ __device__ __forceinline__ void paint_tile(const uint32_t MAXE, const uint32_t S
     const bool in_image = px < P.width && py < P.height;
     uint32_t* out_px = (uint32_t*)image + (size_t)py * P.stride_px + px;
     if (s_solid) {
+        if constexpr (FMT == FMT_F16) {                                 // (no buffer-layer cache with a linear target: the host refuses one)
+            const uint4 w = b_col[0];
+            if (in_image) ((uint2*)image)[(size_t)py * P.stride_px + px] = make_uint2(w.x, w.y);
+            return;
+        }
         const uint32_t bytes = s_solid_bytes;
         if (cache.tiles) {                                              // CachedTile::convert_optimizer_op :690-707
             const bool same = (ct_tags & 1u) && ct_solid == bytes;
@@ -2338,7 +2368,9 @@ __device__ __forceinline__ void paint_tile(const uint32_t MAXE, const uint32_t S
         }
     }
     // ---- compute_srgb :466-483 + channel select, straight to the row-major RGBA8 image ----------------------
-    if (in_image) {
+    if constexpr (FMT == FMT_F16) {                                     // linear target: select, then binary16 (no encode, no clamp)
+        if (in_image) ((uint2*)image)[(size_t)py * P.stride_px + px] = linear_f16x4(P.channels, dr, dg, db, da);
+    } else if (in_image) {
         float sr = linear_to_srgb(dr), sg = linear_to_srgb(dg), sb = linear_to_srgb(db);
         uint32_t out = 0;
 #pragma unroll
@@ -2412,7 +2444,7 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
 // blends, encode) is then spread over four wavefronts with a quarter of the colour registers each: a launch's floor — its
 // deepest tile walked by ONE wavefront — drops accordingly, which is what small frames (1080p, a multi-GPU band) are bound
 // by.  The list work is done four times, so frames that fill the chip with one wavefront per tile keep NPX = 4.
-template <bool SIMPLE, bool ONE_SLICE, int NPX>
+template <bool SIMPLE, bool ONE_SLICE, int NPX, int FMT>
 __global__ __launch_bounds__(64, NPX == 1 ? PAINT_STRIP_OCC : (SIMPLE ? PAINT_SIMPLE_OCC : PAINT_GENERIC_OCC)) void k_paint_wave(PaintParams P, const uint64_t* __restrict__ sorted,
                                                     const TileRecord* __restrict__ records, DevCount nc_runs,
                                                     const uint32_t* __restrict__ tile_first_run,
@@ -2731,6 +2763,17 @@ __global__ __launch_bounds__(64, NPX == 1 ? PAINT_STRIP_OCC : (SIMPLE ? PAINT_SI
             }
         }
         if (ok) {                                                       // TileWriteOp::Solid: to_srgb_bytes :156-162, 690
+            if constexpr (FMT == FMT_F16) {                             // linear target: the selected colour (no cache: the host refuses one)
+                const uint2 v = linear_f16x4(P.channels, dst.r, dst.g, dst.b, dst.a);
+#pragma unroll
+                for (int q = 0; q < NPX; q++) {
+                    const uint32_t py = ty * 16u + (uint32_t)(row0 + q);
+                    if (px < P.width && py < P.height) ((uint2*)image)[(size_t)py * P.stride_px + px] = v;
+                }
+                PP_STAMP(3); PP_COUNT(19, 1);
+                tile_done();
+                return;
+            }
             float sel[4];
 #pragma unroll
             for (int c = 0; c < 4; c++) sel[c] = sel_channel((P.channels >> (8 * c)) & 0xFFu, dst.r, dst.g, dst.b, dst.a);
@@ -2932,6 +2975,16 @@ __global__ __launch_bounds__(64, NPX == 1 ? PAINT_STRIP_OCC : (SIMPLE ? PAINT_SI
         }
     }
     // ---- compute_srgb :466-483 + channel select, straight to the row-major RGBA8 image ----------------------------------
+    if constexpr (FMT == FMT_F16) {                                     // ... or the linear colour, selected on floats, as binary16
+#pragma unroll
+        for (int q = 0; q < NPX; q++) {
+            const uint32_t py = ty * 16u + (uint32_t)(row0 + q);
+            if (px < P.width && py < P.height) ((uint2*)image)[(size_t)py * P.stride_px + px] = linear_f16x4(P.channels, dr[q], dg[q], db[q], da[q]);
+        }
+        PP_STAMP(9);
+        tile_done();                                                    // (no buffer-layer cache with a linear target)
+        return;
+    }
     uint32_t chan_sel = 0;                                              // v_perm_b32 selector: channel.rs:44-55 as byte indices
 #pragma unroll
     for (int c = 0; c < 4; c++) {
@@ -2971,7 +3024,7 @@ __global__ __launch_bounds__(64, NPX == 1 ? PAINT_STRIP_OCC : (SIMPLE ? PAINT_SI
 #ifndef QUAD_ROW_XCD
 #define QUAD_ROW_XCD 1
 #endif
-template <bool ONE_SLICE>
+template <bool ONE_SLICE, int FMT>
 __global__ __launch_bounds__(64, PAINT_SIMPLE_OCC) void k_paint_quad(PaintParams P, const uint64_t* __restrict__ sorted,
                                                                     const TileRecord* __restrict__ records, DevCount nc_runs,
                                                                     const uint32_t* __restrict__ tile_first_run,
@@ -3144,6 +3197,15 @@ __global__ __launch_bounds__(64, PAINT_SIMPLE_OCC) void k_paint_quad(PaintParams
             }
         }
         if (first != 2 && t_in && !over) {                              // TileWriteOp::Solid: to_srgb_bytes :156-162, 690
+            if constexpr (FMT == FMT_F16) {                             // linear target: the selected colour
+                const uint2 v = linear_f16x4(P.channels, dst.r, dst.g, dst.b, dst.a);
+                const uint32_t px = tx * 16u + (uint32_t)li;
+#pragma unroll 4
+                for (int row = 0; row < 16; row++) {
+                    const uint32_t py = ty * 16u + (uint32_t)row;
+                    if (px < P.width && py < P.height) ((uint2*)image)[(size_t)py * P.stride_px + px] = v;
+                }
+            } else {
             float sel[4];
 #pragma unroll
             for (int c = 0; c < 4; c++) sel[c] = sel_channel((P.channels >> (8 * c)) & 0xFFu, dst.r, dst.g, dst.b, dst.a);
@@ -3154,6 +3216,7 @@ __global__ __launch_bounds__(64, PAINT_SIMPLE_OCC) void k_paint_quad(PaintParams
             for (int row = 0; row < 16; row++) {                         // the group's 16 lanes: one pixel column each
                 const uint32_t py = ty * 16u + (uint32_t)row;
                 if (px < P.width && py < P.height) ((uint32_t*)image)[(size_t)py * P.stride_px + px] = bytes;
+            }
             }
         }
     }
@@ -3233,9 +3296,13 @@ __global__ __launch_bounds__(64, PAINT_SIMPLE_OCC) void k_paint_quad(PaintParams
         for (int q = 0; q < 4; q++) {                                   // compute_srgb :466-483 + channel select
             const uint32_t py = ty * 16u + (uint32_t)(rg * 4 + q);
             if (px < P.width && py < P.height) {
+                if constexpr (FMT == FMT_F16) {                         // (linear target: selected on floats, binary16)
+                    ((uint2*)image)[(size_t)py * P.stride_px + px] = linear_f16x4(P.channels, dr[q], dg[q], db[q], da[q]);
+                } else {
                 const float sr = linear_to_srgb(dr[q]), sg = linear_to_srgb(dg[q]), sb2 = linear_to_srgb(db[q]);
                 const uint32_t rgba = to_u8_x8(sr) | (to_u8_x8(sg) << 8) | (to_u8_x8(sb2) << 16) | (to_u8_x8(da[q]) << 24);
                 ((uint32_t*)image)[(size_t)py * P.stride_px + px] = __builtin_amdgcn_perm(0u, rgba, chan_sel);
+                }
             }
         }
     }
@@ -3261,7 +3328,7 @@ __global__ __launch_bounds__(64, PAINT_SIMPLE_OCC) void k_paint_quad(PaintParams
 // 256-lane workgroup per CU — 1 wave per SIMD — painted every tile beyond the wave painters' 128 entries, and the reference
 // demo's own `circles` mode at 20 000 discs (120 layers per tile: half its tiles are "deep") spent 102 us there.
 // STRIDE: the words per entry of `list` (1: tile ids — the wave painters' list; 2: {tile, entries} pairs — the mid tier's).
-template <int MAXE, int STRIDE>
+template <int MAXE, int STRIDE, int FMT>
 __global__ __launch_bounds__(256) void k_paint_deep(PAINT_PARAMS, const uint32_t* __restrict__ list_n,
                                                     const uint32_t* __restrict__ list, uint32_t* __restrict__ over_n,
                                                     uint32_t* __restrict__ over_list) {
@@ -3273,12 +3340,13 @@ __global__ __launch_bounds__(256) void k_paint_deep(PAINT_PARAMS, const uint32_t
     const uint32_t n_runs = dev_count(nc_runs);
     for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
         const uint32_t tile = list[(size_t)STRIDE * i];
-        paint_tile(MAXE, MAXE / 4, e_key, e_tmp, e_flag, PAINT_ARGS2, over_n, over_list);
+        paint_tile<FMT>(MAXE, MAXE / 4, e_key, e_tmp, e_flag, PAINT_ARGS2, over_n, over_list);
         __syncthreads();
     }
 }
 // tiles deeper than the LDS lists: the same code with lists in global memory, sized per tile by the host from the entry
 // counts k_paint_deep recorded (offs[i] = first entry slot of tile i; the staging array is four times as long)
+template <int FMT>
 __global__ __launch_bounds__(256) void k_paint_huge(PAINT_PARAMS, const uint32_t* __restrict__ over2_list, uint32_t n_tiles,
                                                     const uint64_t* __restrict__ offs, uint64_t* __restrict__ g_key,
                                                     uint64_t* __restrict__ g_tmp, uint32_t* __restrict__ g_flag) {
@@ -3287,18 +3355,19 @@ __global__ __launch_bounds__(256) void k_paint_huge(PAINT_PARAMS, const uint32_t
     for (uint32_t i = blockIdx.x; i < n_tiles; i += gridDim.x) {
         const uint32_t tile = over2_list[2 * i], cap = over2_list[2 * i + 1];
         const uint64_t o = offs[i];
-        paint_tile(cap, cap, g_key + 4 * o, g_tmp + o, g_flag + o, PAINT_ARGS2, nullptr, nullptr);
+        paint_tile<FMT>(cap, cap, g_key + 4 * o, g_tmp + o, g_flag + o, PAINT_ARGS2, nullptr, nullptr);
         __syncthreads();
     }
 }
 
-void launch_paint(hipStream_t s, const PaintParams& p, const uint64_t* sorted, const TileRecord* records, DevCount n_runs,
-                  const uint32_t* tile_first_run, const uint32_t* row_span_lo, const uint32_t* row_span_cnt,
-                  const uint64_t* span_key, const uint4* span_cov, const uint4* layer_col,
-                  const uint32_t* style_offsets, const uint32_t* style_words, const forma_image_t* images,
-                  const uint16_t* texels, uint8_t* image, TileCacheArgs cache, FrameInfo* info, uint32_t* overflow_n,
-                  uint32_t* overflow_list, uint32_t* over2_n, uint32_t* over2_list, bool launch_deep, SpanGroups groups, bool strips, bool quads,
-                  uint32_t* mid_n, uint32_t* mid_list, uint32_t n_cus) {
+template <int FMT>
+static void launch_paint_fmt(hipStream_t s, const PaintParams& p, const uint64_t* sorted, const TileRecord* records, DevCount n_runs,
+                             const uint32_t* tile_first_run, const uint32_t* row_span_lo, const uint32_t* row_span_cnt,
+                             const uint64_t* span_key, const uint4* span_cov, const uint4* layer_col,
+                             const uint32_t* style_offsets, const uint32_t* style_words, const forma_image_t* images,
+                             const uint16_t* texels, uint8_t* image, TileCacheArgs cache, FrameInfo* info, uint32_t* overflow_n,
+                             uint32_t* overflow_list, uint32_t* over2_n, uint32_t* over2_list, bool launch_deep, SpanGroups groups, bool strips, bool quads,
+                             uint32_t* mid_n, uint32_t* mid_list, uint32_t n_cus) {
     const uint32_t T = p.tiles_w * p.tiles_h;
     if (T == 0 || p.crop_y1 <= p.crop_y0) return;
     const uint32_t per = paint_band_tiles(p.crop_y1 - p.crop_y0, p.tiles_w);
@@ -3313,12 +3382,12 @@ void launch_paint(hipStream_t s, const PaintParams& p, const uint64_t* sorted, c
     if (quads && simple && !cache.tiles) {
         const uint32_t qper = QUAD_ROW_XCD ? ((p.crop_y1 - p.crop_y0 + 7u) / 8u) * ((p.tiles_w + 3u) / 4u)
                                             : ((p.crop_y1 - p.crop_y0) * ((p.tiles_w + 3u) / 4u) + 7u) / 8u;
-        if (one) FORMA_LAUNCH(k_paint_quad<true>, dim3(qper * 8), dim3(64), 0, s, p, sorted, records, n_runs, tile_first_run, row_span_lo, row_span_cnt,
+        if (one) FORMA_LAUNCH((k_paint_quad<true, FMT>), dim3(qper * 8), dim3(64), 0, s, p, sorted, records, n_runs, tile_first_run, row_span_lo, row_span_cnt,
                               span_key, span_cov, layer_col, image, info, overflow_n, overflow_list, launch_deep ? 1u : 0u, groups);
-        else FORMA_LAUNCH(k_paint_quad<false>, dim3(qper * 8), dim3(64), 0, s, p, sorted, records, n_runs, tile_first_run, row_span_lo, row_span_cnt,
+        else FORMA_LAUNCH((k_paint_quad<false, FMT>), dim3(qper * 8), dim3(64), 0, s, p, sorted, records, n_runs, tile_first_run, row_span_lo, row_span_cnt,
                           span_key, span_cov, layer_col, image, info, overflow_n, overflow_list, launch_deep ? 1u : 0u, groups);
     } else {
-#define PW_LAUNCH(S_, O_, N_) FORMA_LAUNCH((k_paint_wave<S_, O_, N_>), dim3(N_ == 1 ? per * 32 : (per + (p.order_cnt_out ? p.order_hcap : 0u)) * 8), dim3(64), 0, s, p, sorted, records, n_runs, \
+#define PW_LAUNCH(S_, O_, N_) FORMA_LAUNCH((k_paint_wave<S_, O_, N_, FMT>), dim3(N_ == 1 ? per * 32 : (per + (p.order_cnt_out ? p.order_hcap : 0u)) * 8), dim3(64), 0, s, p, sorted, records, n_runs, \
                                              tile_first_run, row_span_lo, row_span_cnt, span_key, span_cov, layer_col, style_offsets, style_words, \
                                              images, texels, image, cache, info, overflow_n, overflow_list, launch_deep ? 1u : 0u, groups)
 #define PW_LAUNCH_N(S_, O_) do { if (strips) PW_LAUNCH(S_, O_, 1); else PW_LAUNCH(S_, O_, 4); } while (0)
@@ -3331,12 +3400,26 @@ void launch_paint(hipStream_t s, const PaintParams& p, const uint64_t* sorted, c
     // mid tier: four workgroups per CU; its own overflow ({tile, entries} pairs in mid_list) goes to the 4096-entry tier, whose
     // launch is empty (~4 us) in every frame without a tile beyond 1024 entries — paid only by frames that have deep tiles at all
     const uint32_t g_mid = std::min<uint32_t>(T, 4u * n_cus), g_deep = std::min<uint32_t>(T, n_cus);
-    FORMA_LAUNCH((k_paint_deep<PAINT_MAXE_MID, 1>), dim3(g_mid), dim3(256), 0, s, p, sorted, records, n_runs, tile_first_run,
+    FORMA_LAUNCH((k_paint_deep<PAINT_MAXE_MID, 1, FMT>), dim3(g_mid), dim3(256), 0, s, p, sorted, records, n_runs, tile_first_run,
                        row_span_lo, row_span_cnt, span_key, span_cov, layer_col, style_offsets, style_words, images,
                        texels, image, cache, info, (const uint32_t*)overflow_n, (const uint32_t*)overflow_list, mid_n, mid_list);
-    FORMA_LAUNCH((k_paint_deep<PAINT_MAXE_DEEP, 2>), dim3(g_deep), dim3(256), 0, s, p, sorted, records, n_runs, tile_first_run,
+    FORMA_LAUNCH((k_paint_deep<PAINT_MAXE_DEEP, 2, FMT>), dim3(g_deep), dim3(256), 0, s, p, sorted, records, n_runs, tile_first_run,
                        row_span_lo, row_span_cnt, span_key, span_cov, layer_col, style_offsets, style_words, images,
                        texels, image, cache, info, (const uint32_t*)mid_n, (const uint32_t*)mid_list, over2_n, over2_list);
+}
+void launch_paint(hipStream_t s, const PaintParams& p, const uint64_t* sorted, const TileRecord* records, DevCount n_runs,
+                  const uint32_t* tile_first_run, const uint32_t* row_span_lo, const uint32_t* row_span_cnt,
+                  const uint64_t* span_key, const uint4* span_cov, const uint4* layer_col,
+                  const uint32_t* style_offsets, const uint32_t* style_words, const forma_image_t* images,
+                  const uint16_t* texels, uint8_t* image, TileCacheArgs cache, FrameInfo* info, uint32_t* overflow_n,
+                  uint32_t* overflow_list, uint32_t* over2_n, uint32_t* over2_list, bool launch_deep, SpanGroups groups, bool strips, bool quads,
+                  uint32_t* mid_n, uint32_t* mid_list, uint32_t n_cus, uint32_t fmt) {
+#define LP_ARGS s, p, sorted, records, n_runs, tile_first_run, row_span_lo, row_span_cnt, span_key, span_cov, layer_col, style_offsets, \
+                style_words, images, texels, image, cache, info, overflow_n, overflow_list, over2_n, over2_list, launch_deep, groups, strips, \
+                quads, mid_n, mid_list, n_cus
+    if (fmt == FORMA_FORMAT_LINEAR_F16) launch_paint_fmt<FMT_F16>(LP_ARGS);
+    else launch_paint_fmt<FMT_SRGB8>(LP_ARGS);
+#undef LP_ARGS
 }
 
 void launch_paint_huge(hipStream_t s, const PaintParams& p, const uint64_t* sorted, const TileRecord* records, DevCount n_runs,
@@ -3344,11 +3427,16 @@ void launch_paint_huge(hipStream_t s, const PaintParams& p, const uint64_t* sort
                        const uint64_t* span_key, const uint4* span_cov, const uint4* layer_col,
                        const uint32_t* style_offsets, const uint32_t* style_words, const forma_image_t* images,
                        const uint16_t* texels, uint8_t* image, TileCacheArgs cache, FrameInfo* info, const uint32_t* over2_list,
-                       uint32_t n_tiles, const uint64_t* offs, uint64_t* g_key, uint64_t* g_tmp, uint32_t* g_flag) {
+                       uint32_t n_tiles, const uint64_t* offs, uint64_t* g_key, uint64_t* g_tmp, uint32_t* g_flag, uint32_t fmt) {
     if (n_tiles == 0) return;
-    FORMA_LAUNCH(k_paint_huge, dim3(n_tiles < 256 ? n_tiles : 256), dim3(256), 0, s, p, sorted, records, n_runs, tile_first_run,
-                       row_span_lo, row_span_cnt, span_key, span_cov, layer_col, style_offsets, style_words, images, texels, image,
-                       cache, info, over2_list, n_tiles, offs, g_key, g_tmp, g_flag);
+    if (fmt == FORMA_FORMAT_LINEAR_F16)
+        FORMA_LAUNCH((k_paint_huge<FMT_F16>), dim3(n_tiles < 256 ? n_tiles : 256), dim3(256), 0, s, p, sorted, records, n_runs, tile_first_run,
+                     row_span_lo, row_span_cnt, span_key, span_cov, layer_col, style_offsets, style_words, images, texels, image,
+                     cache, info, over2_list, n_tiles, offs, g_key, g_tmp, g_flag);
+    else
+        FORMA_LAUNCH((k_paint_huge<FMT_SRGB8>), dim3(n_tiles < 256 ? n_tiles : 256), dim3(256), 0, s, p, sorted, records, n_runs, tile_first_run,
+                     row_span_lo, row_span_cnt, span_key, span_cov, layer_col, style_offsets, style_words, images, texels, image,
+                     cache, info, over2_list, n_tiles, offs, g_key, g_tmp, g_flag);
 }
 
 // ================================================================================================

@@ -237,6 +237,43 @@ int forma_hip_render(forma_hip_ctx* ctx, uint8_t* dst, uint32_t width, uint32_t 
 int forma_hip_render_enqueue(forma_hip_ctx* ctx, uint8_t* dst, uint32_t width, uint32_t height,
                              size_t stride_bytes, const uint8_t channels[4],
                              const float clear_color[4], const forma_rect_t* crop_or_null);
+/* forma_hip_render into caller DEVICE memory: the GPU backend's `Renderer::render_to_texture` (reference
+ * forma/src/gpu/renderer/mod.rs:462-520), for consumers that stay on the GPU (a torch model fed with rendered frames, a
+ * compositor, a video encoder).  The painters' image pointer IS `dst_device`: no copy kernel, no memcpy, no PCIe traffic; a
+ * device frame launches the same kernels as a `dst == NULL` frame.
+ *   format        FORMA_FORMAT_SRGB8: 4 B/pixel, byte for byte what forma_hip_render writes for the same frame, channels, clear
+ *                 colour, crop and cache.  FORMA_FORMAT_LINEAR_F16: 8 B/pixel, 4 x IEEE binary16: `channels.map(select(r, g, b,
+ *                 a))` of the painter's LINEAR colour where the u8 path calls compute_srgb (cpu/painter/mod.rs:466-483) — for a
+ *                 TileWriteOp::Solid tile the colour the u8 path hands to to_srgb_bytes — with no sRGB encode and no clamp (the
+ *                 reference's GPU store into its Rgba16Float target, gpu/painter/paint.wgsl:954, gpu/renderer/mod.rs:176-191),
+ *                 f32 -> f16 rounded to nearest even; Zero is 0.0, One is 1.0.
+ *   dst_device    device memory of the context's own device (hipPointerGetAttributes); host, pinned-host, managed or another
+ *                 device's memory is FORMA_E_ARG, and so is a pointer this library's HIP runtime does not know (a process that
+ *                 loads a second copy of the runtime, e.g. torch imported after this library).  Aligned to the pixel size, and
+ *                 the whole canvas, (height - 1) * stride_bytes + width * bpp bytes, lies inside its allocation.
+ *   stride_bytes  >= width * bpp and a multiple of bpp, else FORMA_E_ARG.
+ *   written       only the tile-rounded crop clipped to the canvas; every other byte of the target is left alone.
+ *   cache_id      >= 0 for SRGB8 only (the reference's GPU renderer has no layer cache): FORMA_E_ARG with LINEAR_F16.  The
+ *                 painter writes straight into `dst_device` and skips the tiles the optimizer passes skip (TileWriteOp::None),
+ *                 so the target must still hold what this cache painted into it last frame (a BufferLayerCache belongs to one
+ *                 Buffer).  Each cache remembers what it last painted into — the caller's host buffer or a (pointer, stride)
+ *                 target — and clears its tile state when that changes, as on a size change (cpu/renderer.rs:94-111).
+ *   wait_stream   a hipStream_t (NULL: the null stream): the frame's first write into `dst_device` is ordered after all work
+ *                 enqueued there before the call (an event, no host wait).
+ *   completion    one frame slot, a cache or `timings`: complete when the call returns.  n > 1 frame slots without cache and
+ *                 timings: enqueued exactly like forma_hip_render_enqueue — `dst_device` is complete after forma_hip_sync or n
+ *                 further frames, and its contents are undefined until then (a frame whose read-back-free prediction failed is
+ *                 re-run into the same target when it is settled).
+ *   afterwards    forma_hip_read_image returns FORMA_E_STATE (the image lives in caller memory); _tiles_written, _read_segments
+ *                 and _kernel_times work as after any frame.
+ * A multi-device context returns FORMA_E_STATE. */
+#define FORMA_FORMAT_SRGB8      0u   /* 4 B/pixel: exactly the bytes forma_hip_render writes        */
+#define FORMA_FORMAT_LINEAR_F16 1u   /* 8 B/pixel: 4 x IEEE binary16, the painter's linear colour   */
+int forma_hip_render_device(forma_hip_ctx* ctx, void* dst_device, uint32_t format,
+                            uint32_t width, uint32_t height, size_t stride_bytes,
+                            const uint8_t channels[4], const float clear_color[4],
+                            const forma_rect_t* crop_or_null, int cache_id,
+                            void* wait_stream /* hipStream_t or NULL */, forma_timings_t* timings);
 /* Page-lock a caller buffer the renderer writes often (hipHostRegister): copies into it are asynchronous and run at the
  * link's rate.  The caller keeps the memory alive until forma_hip_unregister_buffer (which waits for frames in flight) or
  * forma_hip_destroy. */

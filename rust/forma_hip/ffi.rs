@@ -21,6 +21,10 @@ pub const FORMA_E_COMM: c_int = -7;
 
 pub const FORMA_GEOM_HAS_XF: u32 = 1;
 
+// forma_hip_render_device target formats
+pub const FORMA_FORMAT_SRGB8: u32 = 0;
+pub const FORMA_FORMAT_LINEAR_F16: u32 = 1;
+
 pub const FORMA_FILL_SOLID: u32 = 0;
 pub const FORMA_FILL_LINEAR: u32 = 1;
 pub const FORMA_FILL_RADIAL: u32 = 2;
@@ -288,6 +292,20 @@ extern "C" {
         channels: *const u8,
         clear_color: *const f32,
         crop_or_null: *const forma_rect_t,
+    ) -> c_int;
+    pub fn forma_hip_render_device(
+        ctx: *mut forma_hip_ctx,
+        dst_device: *mut c_void,
+        format: u32,
+        width: u32,
+        height: u32,
+        stride_bytes: usize,
+        channels: *const u8,
+        clear_color: *const f32,
+        crop_or_null: *const forma_rect_t,
+        cache_id: c_int,
+        wait_stream: *mut c_void,
+        timings: *mut forma_timings_t,
     ) -> c_int;
     pub fn forma_hip_register_buffer(ctx: *mut forma_hip_ctx, ptr: *mut c_void, bytes: usize) -> c_int;
     pub fn forma_hip_unregister_buffer(ctx: *mut forma_hip_ctx, ptr: *mut c_void) -> c_int;

@@ -459,6 +459,56 @@ impl Renderer {
         }
     }
 
+    /// `gpu::Renderer::render_to_texture` (`gpu/renderer/mod.rs:462-520`): paint straight into caller device memory of
+    /// this renderer's GPU — `height` rows of `stride_bytes`, `format` = `ffi::FORMA_FORMAT_SRGB8` (the bytes `render`
+    /// writes) or `ffi::FORMA_FORMAT_LINEAR_F16` (the painter's linear colour, 4 x binary16).  The frame's writes wait for the
+    /// work enqueued on `wait_stream` (a `hipStream_t`, null: the null stream).  No layer cache: the GPU backend has none.
+    ///
+    /// # Safety
+    /// `dst_device` must stay allocated until the frame is complete: when this returns with one frame in flight, after
+    /// `forma_hip_sync` with several.
+    pub unsafe fn render_to_device(
+        &mut self,
+        composition: &mut Composition,
+        dst_device: *mut std::ffi::c_void,
+        format: u32,
+        width: usize,
+        height: usize,
+        stride_bytes: usize,
+        channels: [Channel; 4],
+        clear_color: Color,
+        crop: Option<Rect>,
+        wait_stream: *mut std::ffi::c_void,
+    ) {
+        // renderer.rs:113-118, as in `render`.
+        composition.compact_geom();
+        composition.shared_state.borrow_mut().props_interner.compact();
+
+        self.upload_geometry(composition);
+        self.upload_tables(composition, None);
+
+        let channels = channel_codes(channels, clear_color);
+        let clear = [clear_color.r, clear_color.g, clear_color.b, clear_color.a];
+        let rect = pixel_rect(crop.as_ref(), width, height);
+        let rect_ptr = rect.as_ref().map_or(ptr::null(), |rect| rect as *const forma_rect_t);
+
+        let rc = ffi::forma_hip_render_device(
+            self.ctx,
+            dst_device,
+            format,
+            width as u32,
+            height as u32,
+            stride_bytes,
+            channels.as_ptr(),
+            clear.as_ptr(),
+            rect_ptr,
+            -1,
+            wait_stream,
+            &mut self.timings,
+        );
+        self.check(rc, "forma_hip_render_device");
+    }
+
     fn read_tile_flags(&mut self, tiles_len: usize) {
         self.tile_flags.resize(tiles_len, 0);
         // SAFETY: `tile_flags` holds `tiles_len` bytes.

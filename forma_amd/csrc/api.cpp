@@ -323,13 +323,14 @@ int plan_zero_jobs(forma_hip_ctx* ctx, uint32_t width, uint32_t height, uint32_t
     const uint32_t tiles_w = (width + 15) / 16, tiles_h = (height + 15) / 16;
     const SortPlan plan = frame_sort_plan(ctx, ctx->pred_live44, ctx->pred_layer_sorted, ctx->digit_bits, true, nullptr);
     HIPCHECK(ctx->sort_counters.ensure(sort_scratch_words(std::max<size_t>(sort_n, 1)) * 4));
-    HIPCHECK(ctx->row_tab.ensure(row_tab_total_words(tiles_w, tiles_h) * 4));
+    HIPCHECK(ctx->row_tab.ensure(frame_tables(nullptr, tiles_w, tiles_h).total_words * 4));
+    const FrameTables tab = frame_tables(ctx->row_tab.as<uint32_t>(), tiles_w, tiles_h);
     HIPCHECK(ctx->runs_scratch.ensure(runs_scratch_words(std::max<size_t>(runs_n, 1)) * 4));
     const size_t sw = sort_n > 1 && plan.n_passes ? sort_zero_words(sort_n, plan) : 0;
-    const size_t tw = row_tab_zero_words(tiles_w, tiles_h);
+    const size_t tw = tab.zero_words;
     if (sw > 0xFFFFFFFFull || tw > 0xFFFFFFFFull) return FORMA_OK;           // (absurd sizes: the stages clear for themselves)
     if (sw) { Z->p[Z->n] = ctx->sort_counters.as<uint32_t>(); Z->words[Z->n++] = (uint32_t)sw; cleared->sort_p = ctx->sort_counters.p; cleared->sort_words = sw; }
-    Z->p[Z->n] = ctx->row_tab.as<uint32_t>(); Z->words[Z->n++] = (uint32_t)tw; cleared->tab_p = ctx->row_tab.p; cleared->tab_words = tw;
+    Z->p[Z->n] = tab.row_count; Z->words[Z->n++] = (uint32_t)tw; cleared->tab_p = ctx->row_tab.p; cleared->tab_words = tw;
     // (the status words of the chained run kernel: a word per 2 048 segments)
     const size_t cw = runs_n ? runs_chain_words(runs_n) : 0;
     if (cw && cw <= 0xFFFFFFFFull) { Z->p[Z->n] = ctx->runs_scratch.as<uint32_t>(); Z->words[Z->n++] = (uint32_t)cw; cleared->chain_p = ctx->runs_scratch.p; cleared->chain_words = cw; }
@@ -411,8 +412,16 @@ struct PaintArgs {
     uint8_t* target = nullptr;
     size_t target_pitch = 0;
     uint32_t fmt = FORMA_FORMAT_SRGB8;
+    uint32_t tiles_w() const { return (width + 15) / 16; }  uint32_t tiles_h() const { return (height + 15) / 16; }
 };
 
+// the frame's crop in tiles, clamped to the tile rectangle [x0, x1) x [y0, y1) of the canvas (Rect::new, renderer.rs:43-52)
+struct TileRect { uint32_t x0, x1, y0, y1; };
+TileRect crop_tiles(const PaintArgs& a) {
+    const uint32_t tiles_w = a.tiles_w(), tiles_h = a.tiles_h();
+    if (!a.crop) return TileRect{0, tiles_w, 0, tiles_h};
+    return TileRect{a.crop->x0 / 16, std::min(tiles_w, (a.crop->x1 + 15) / 16), a.crop->y0 / 16, std::min(tiles_h, (a.crop->y1 + 15) / 16)};
+}
 // A synchronous frame into caller memory is PCIe from the painter's last tile on: 33 MB of a 4K image take ~600 us behind ~450 us
 // of kernels.  Painted in bands of tile rows — one launch and one event per band — the first band's pixels leave after an
 // eighth of the painter instead, on a second stream, and the link is busy while the rest is painted (the copies then end ~70 us
@@ -442,19 +451,11 @@ int split_plan(forma_hip_ctx* ctx, const PaintArgs& a, const PaintParams& P, uin
     return (int)std::min<uint32_t>(forced ? (uint32_t)ctx->dbg.paint_split : 2u, rows);   // (the policy: two bands, run_paint places the cut)
 }
 
-// stage 4 on ctx->sorted (n segments): runs + carry pre-pass + per-tile painter -> ctx->image
-// bound_j != 0: asynchronous — the run count stays on the device (info->n_runs), buffers are provisioned for bound_j runs.
-int run_paint(forma_hip_ctx* ctx, DevCount nc, const PaintArgs& a, bool timing, uint32_t bound_j = 0) {
-    const size_t n = nc.bound;
-    // set_styles and set_images are separate calls: the image a texture style names is checked where both are known
-    if (ctx->any_texture && ctx->max_image_index >= ctx->n_images) return fail(ctx, FORMA_E_ARG, "texture style names an image that was not uploaded");
-    const uint32_t tiles_w = (a.width + 15) / 16, tiles_h = (a.height + 15) / 16;
-    const uint32_t T = tiles_w * tiles_h;
-    ctx->img_w = a.width; ctx->img_h = a.height;
-    ctx->chain_rows = nullptr; ctx->n_chain_rows = 0;
-    // where this frame is painted: the cache's own image (it must keep what its buffer showed last frame) or the scratch one
-    TileCacheArgs tc{nullptr, nullptr};
-    uint32_t clear_unchanged = 0;
+// where this frame is painted: the cache's own image (it must keep what its buffer showed last frame), a device target or the scratch one
+struct PaintTarget { TileCacheArgs tc; uint32_t clear_unchanged; /* PaintParams::clear_unchanged */ };
+int paint_target(forma_hip_ctx* ctx, const PaintArgs& a, PaintTarget* out) {
+    const uint32_t T = a.tiles_w() * a.tiles_h();
+    *out = PaintTarget{TileCacheArgs{nullptr, nullptr}, 0u};
     ctx->cur_cache = a.cache_id;
     ctx->image_external = a.target != nullptr;
     if (a.cache_id >= 0) {
@@ -470,8 +471,8 @@ int run_paint(forma_hip_ctx* ctx, DevCount nc, const PaintArgs& a, bool timing, 
             if (!a.target) HIPCHECK(hipMemsetAsync(c.image.p, 0, (size_t)a.width * a.height * 4, ctx->stream));
         }
         HIPCHECK(hipMemsetAsync(ctx->cache_written.p, 0, (size_t)T, ctx->stream));
-        tc.tiles = c.tiles.as<uint2>(); tc.written = ctx->cache_written.as<uint8_t>();
-        clear_unchanged = c.has_clear && memcmp(c.clear, a.clear, sizeof c.clear) == 0 ? 1u : 0u;
+        out->tc = TileCacheArgs{c.tiles.as<uint2>(), ctx->cache_written.as<uint8_t>()};
+        out->clear_unchanged = c.has_clear && memcmp(c.clear, a.clear, sizeof c.clear) == 0 ? 1u : 0u;
         ctx->cur_image = a.target ? a.target : c.image.as<uint8_t>();
     } else if (a.target) {
         ctx->cur_image = a.target;
@@ -479,33 +480,39 @@ int run_paint(forma_hip_ctx* ctx, DevCount nc, const PaintArgs& a, bool timing, 
         HIPCHECK(ctx->image.ensure((size_t)a.width * a.height * 4));
         ctx->cur_image = ctx->image.as<uint8_t>();
     }
-    // one buffer, zeroed by ONE memset per frame (launch_runs; layout: row_tab_zero_words in common.h): [row_count: tiles_h + 1]
-    // [row_span_lo | row_span_cnt: one pair per (row, slice of the carry pre-pass), 8 tiles_h + 1 each] [painter overflow
-    // counters: wave -> deep, deep -> huge] [first-run table, T words]; the painter's overflow lists (T words of tiles, 2 T
-    // words of {tile, entries}) follow un-zeroed
-    HIPCHECK(ctx->row_tab.ensure(row_tab_total_words(tiles_w, tiles_h) * 4));
-    FrameInfo* dinfo = ctx->info.as<FrameInfo>();
-    uint32_t* row_count = ctx->row_tab.as<uint32_t>();
-    uint32_t* row_span_lo = row_count + (tiles_h + 1);
-    uint32_t* row_span_cnt = row_span_lo + (CR_MAX_SLICES_HOST * tiles_h + 1);
-    uint32_t* paint_overflow = row_span_cnt + (CR_MAX_SLICES_HOST * tiles_h + 1);   // [0], [1], [2] = the three counts (wave -> mid, deep -> huge, mid -> deep), then the first-run table ...
-    uint32_t* over2_n = paint_overflow + 1;
-    uint32_t* mid_n = paint_overflow + 2;
-    uint32_t* tile_first_run = paint_overflow + 3;
-    uint32_t* order_cnt = tile_first_run + T;                           // ... the painters' order counts (PaintParams::order_cnt_out) ...
-    uint32_t* overflow_list = order_cnt + PAINT_ORDER_WORDS;            // ... then the lists themselves
-    uint32_t* over2_list = overflow_list + T;
-    uint32_t* row_base = over2_list + 2 * (size_t)T;                    // (chain numbering: where each row's runs begin)
-    uint32_t* mid_list = row_base + (tiles_h + 1);                      // {tile, entries} of the tiles beyond the mid tier's lists: 2 T words
-    uint32_t J = 0;
-    HIPCHECK(ctx->blk_edge.ensure(runs_blocks(std::max<size_t>(n, 1)) * sizeof(BlkEdge)));
-    HIPCHECK(ctx->runs_scratch.ensure(runs_scratch_words(std::max<size_t>(n, 1)) * 4));
-    stage_begin(ctx, ST_CARRY, timing);
-    const bool tables_zero = ctx->pz.tab_p == ctx->row_tab.p && ctx->pz.tab_words >= row_tab_zero_words(tiles_w, tiles_h);
-    ctx->pz.tab_p = nullptr;
+    return FORMA_OK;
+}
+// How the frame's runs are numbered (launch_runs) and which carry kernel orders them (launch_carry_rows)
+struct CarryPlan {
+    bool local_sort;                        // the rows' runs are ordered inside k_carry_rows (else by a global radix sort)
+    bool chain, chain_zero, blk;            // numbered per tile row (its status words cleared by the frame's first kernel) / per 2 048-segment tile
+    uint32_t rows_painted, n_slices;        // tile rows the carry pre-pass visits, its workgroups per row
+    bool small, half, covl;                 // the carry kernel's variant
+};
+// Slicing pays when a row is heavy (measured on a 17-row band of the 4K scene, 4 800 runs per row: carry stage 80 -> 57 us
+// with eight small workgroups per row) and costs when it is light (a 64-row band of the 8192 x 8192 scene, ~1 000 runs per
+// row: 48 -> 55 us): a slice should keep >= ~768 runs.
+static uint32_t slices_for(uint32_t per_cu_budget, uint32_t rows_painted, uint32_t max_row) {
+    const uint32_t by_chip = std::max(1u, per_cu_budget / rows_painted), by_load = std::max(1u, max_row / 768u);
+    return std::min<uint32_t>(CR_MAX_SLICES_HOST, std::min(by_chip, by_load));
+}
+// COVL (paint.hip): a row in ONE slice whose runs fit carry_rows_covl_cap() — the 4K scene's 4 800 — stages its cover sums
+// and style summaries in LDS before the walk.  A read-back-free frame guesses from the last verified frame's heaviest row
+// (6 % head-room); a row beyond the cap voids the frame and the synchronous re-run knows the rows.
+// (the 512-lane variant for light rows in one slice — the 8K triangle scene — has the room as well: 32 KB of covers, two
+//  workgroups per CU instead of three, still one round for 512 rows)
+static bool covl_choice(const forma_hip_ctx* ctx, const CarryPlan& cp, uint32_t slices, bool async) {
+    const uint32_t mxr = ctx->pred_max_row;
+    const bool big = !cp.small && !cp.half && mxr != 0xFFFFFFFFu &&
+                     (async ? !ctx->covl_banned && (uint64_t)mxr + mxr / 64u <= carry_rows_covl_cap() : mxr <= carry_rows_covl_cap());
+    return cp.local_sort && slices == 1u && ctx->dbg.carry_covl != 0 && (big || (cp.small && cp.half && (ctx->dbg.carry_covl & 2) == 0));
+}
+// the plan before any run is counted: a read-back-free frame (bound_j != 0) decides from the last verified frame
+CarryPlan plan_carry(forma_hip_ctx* ctx, const PaintArgs& a, size_t n, uint32_t bound_j) {
+    CarryPlan cp{};
     // the rows' runs are ordered inside k_carry_rows when they fit its LDS; else by a global sort
     // (the in-LDS key holds 16 layer bits: every order a geom can produce has to fit, not just the style table)
-    bool local_sort = ctx->n_orders <= 65536 && ctx->max_geom_order < 65536 && !ctx->global_runsort;
+    cp.local_sort = ctx->n_orders <= 65536 && ctx->max_geom_order < 65536 && !ctx->global_runsort;
     // A read-back-free frame whose rows are ordered in LDS needs no dense run numbering (the global run sort does): its runs are
     // found by ONE kernel, numbered per tile row from the index of the row's first segment (launch_runs' chain) — no counting
     // pass, the sorted stream is read once less.  The record arrays are then indexed like the segments: provisioned for N.
@@ -514,70 +521,54 @@ int run_paint(forma_hip_ctx* ctx, DevCount nc, const PaintArgs& a, bool timing, 
     // rounds of workgroups pays it in every round (4K: 23.8 + 52.8 -> 84.8 us, 8K: 16.4 + 31.0 -> 54.5) — those keep the counting pass.
     // With several frames in flight the waves that wait take issue slots from the other frames' kernels (1080p, three slots:
     // 9 942 -> 9 707 frames/s while the call alone gains 2.6 %): one frame in flight only, like the strip painters.
-    const bool chain = bound_j != 0 && n > 0 && local_sort && ctx->pred_max_row <= carry_rows_local_cap() &&
-                       (ctx->dbg.runs_chain < 0 ? (RUNS_CHAIN_DEFAULT != 0 && runs_chain_words(n) <= RUNS_CHAIN_MAX_TILES && one_frame_in_flight(ctx))
-                                                : ctx->dbg.runs_chain != 0);
-    const bool chain_zero = chain && ctx->pz.chain_p == ctx->runs_scratch.p && ctx->pz.chain_words >= runs_chain_words(n);
+    cp.chain = bound_j != 0 && n > 0 && cp.local_sort && ctx->pred_max_row <= carry_rows_local_cap() &&
+               (ctx->dbg.runs_chain < 0 ? (RUNS_CHAIN_DEFAULT != 0 && runs_chain_words(n) <= RUNS_CHAIN_MAX_TILES && one_frame_in_flight(ctx))
+                                        : ctx->dbg.runs_chain != 0);
+    cp.chain_zero = cp.chain && ctx->pz.chain_p == ctx->runs_scratch.p && ctx->pz.chain_words >= runs_chain_words(n);
     ctx->pz.chain_p = nullptr;
-    DevCount jc;
     // Several workgroups share a tile row, each a range of layers (k_carry_rows): as many as keep the chip busy for the rows
     // this frame paints (a multi-GPU band is a fraction of the canvas).  The small-LDS variant (a quarter of the keys per workgroup) is a
     // read-back-free frame's guess — its slices must fit 4096 runs, known only from a previous frame; a slice that does not
     // fit voids the frame (plan_bad), the synchronous re-run takes the large variant, and the guess is not made again.
-    uint32_t crow0 = 0, crow1 = tiles_h;                    // the tile rows the painter visits (Rect::new, renderer.rs:43-52)
-    if (a.crop) { crow0 = a.crop->y0 / 16; crow1 = std::min(tiles_h, (a.crop->y1 + 15) / 16); }
-    const uint32_t rows_painted = std::max(crow1 > crow0 ? crow1 - crow0 : 0u, 1u);
-    ctx->cur_rows_painted = rows_painted;
-    // Slicing pays when a row is heavy (measured on a 17-row band of the 4K scene, 4 800 runs per row: carry stage 80 -> 57 us
-    // with eight small workgroups per row) and costs when it is light (a 64-row band of the 8192 x 8192 scene, ~1 000 runs per
-    // row: 48 -> 55 us): a slice should keep >= ~768 runs.
-    auto slices_for = [&](uint32_t per_cu_budget, uint32_t max_row) {
-        const uint32_t by_chip = std::max(1u, per_cu_budget / rows_painted), by_load = std::max(1u, max_row / 768u);
-        return std::min<uint32_t>(CR_MAX_SLICES_HOST, std::min(by_chip, by_load));
-    };
-    uint32_t n_slices = 1;
-    bool small = false, half = false, covl = false;
+    const TileRect crop = crop_tiles(a);                  // (the tile rows the painter visits)
+    cp.rows_painted = std::max(crop.y1 > crop.y0 ? crop.y1 - crop.y0 : 0u, 1u);
+    ctx->cur_rows_painted = cp.rows_painted;
+    cp.n_slices = 1;
     if (bound_j) {
-        local_sort = local_sort && ctx->pred_max_row <= carry_rows_local_cap();     // wrong guess -> plan_bad -> synchronous re-run
+        cp.local_sort = cp.local_sort && ctx->pred_max_row <= carry_rows_local_cap();     // wrong guess -> plan_bad -> synchronous re-run
         const uint32_t pmr = ctx->pred_max_row == 0xFFFFFFFFu ? 0u : ctx->pred_max_row;
-        n_slices = slices_for(256u, pmr);
-        const uint32_t ks = slices_for(512u, pmr);
+        cp.n_slices = slices_for(256u, cp.rows_painted, pmr);
+        const uint32_t ks = slices_for(512u, cp.rows_painted, pmr);
         // (a whole 4K frame — 135 rows, one workgroup each — gains nothing from three small workgroups per row and its painters
         //  pay for the extra span lists: measured 124 -> 126 us carry, 133 -> 139 us paint; bands of <= 128 rows do gain)
-        if (local_sort && ks > 1u && rows_painted <= 128u && !ctx->small_banned && !ctx->no_small_carry && !ctx->force_slices) {
+        if (cp.local_sort && ks > 1u && cp.rows_painted <= 128u && !ctx->small_banned && !ctx->no_small_carry && !ctx->force_slices) {
             const bool known = ctx->pred_slice_n == ks && ctx->pred_slice_small;
             const uint64_t guess = known ? (uint64_t)ctx->pred_max_slice * 10 / 9 : (uint64_t)ctx->pred_max_row * 5 / (3 * ks);
-            if (guess <= carry_rows_small_cap()) { small = true; n_slices = ks; }
+            if (guess <= carry_rows_small_cap()) { cp.small = true; cp.n_slices = ks; }
             // ... as 512-lane workgroups when the slices fit those AND the frame is many workgroups (the painters see the same ks
             // span lists either way).  Two measurements stand behind the count: 1080p, 68 rows x 3 slices of ~900 runs: 36.1 -> 27.3 us,
             // +4.7 % frames/s per call, +8.8 % with three slots; a 17-row band of the 4K scene, 6 slices of ~800 runs each with
             // long span lists: 25.4 -> 29.1 us — a hundred workgroups have a CU each and the 1 024-lane one finishes its slice sooner.
-            if (small && CARRY_HALF_SLICED && ctx->dbg.carry_half == 1 && guess <= carry_rows_half_cap() && rows_painted * ks >= 192u) half = true;
+            if (cp.small && CARRY_HALF_SLICED && ctx->dbg.carry_half == 1 && guess <= carry_rows_half_cap() && cp.rows_painted * ks >= 192u) cp.half = true;
         }
         // The HALF variant (512 lanes, one piece of <= 2048 runs, three workgroups per CU) for frames whose rows are LIGHT — the
         // 8192 x 8192 triangle scene (512 rows of ~1 000 runs), 1080p: one workgroup per row as before, but 768 of them resident
         // at once instead of 256, each without the large variant's 148 KB of LDS to itself (carry 57 -> 32 us on the 8K scene,
         // 42 -> 27 at 1080p).  Heavy rows (the 4K scene: 4 800 runs) gain nothing from 3-6 half workgroups per row — measured:
         // the carry kernel saves 0-12 us and the painters pay as much for the extra span lists.
-        if (!small && local_sort && !ctx->small_banned && !ctx->no_small_carry && !ctx->force_slices && ctx->dbg.carry_half != 0 && pmr) {
+        if (!cp.small && cp.local_sort && !ctx->small_banned && !ctx->no_small_carry && !ctx->force_slices && ctx->dbg.carry_half != 0 && pmr) {
             uint32_t kh = 1u;
             if (ctx->dbg.carry_half > 1) kh = (uint32_t)std::min<int>(ctx->dbg.carry_half, (int)CR_MAX_SLICES_HOST);   // (tools: N slices per row)
             const bool known = ctx->pred_slice_n == kh && ctx->pred_slice_small && ctx->pred_slice_half;
             const uint64_t guess = known ? (uint64_t)ctx->pred_max_slice * 10 / 9 : (kh > 1u ? (uint64_t)pmr * 5 / (3 * kh) : (uint64_t)pmr * 6 / 5);
-            if (guess <= carry_rows_half_cap()) { small = true; half = true; n_slices = kh; }
+            if (guess <= carry_rows_half_cap()) { cp.small = true; cp.half = true; cp.n_slices = kh; }
         }
-        ctx->small_tried = small;
+        ctx->small_tried = cp.small;
     }
     // BLOCKS (launch_runs, k_carry_rows): a read-back-free frame whose tile rows take ONE carry workgroup each needs neither the counting
     // pass nor the chain: the run kernel numbers per 2 048-segment tile into sparse arrays and the row's workgroup compacts them.
-    const uint32_t ns_final = ctx->force_slices ? std::min<uint32_t>(ctx->force_slices, CR_MAX_SLICES_HOST) : n_slices;
-    // (... and takes a COVL variant of the carry kernel — decided below, from the same predictions)
-    auto covl_choice = [&](uint32_t slices) {
-        const uint32_t mxr = ctx->pred_max_row;
-        const bool big = !small && !half && mxr != 0xFFFFFFFFu &&
-                         (bound_j ? !ctx->covl_banned && (uint64_t)mxr + mxr / 64u <= carry_rows_covl_cap() : mxr <= carry_rows_covl_cap());
-        return local_sort && slices == 1u && ctx->dbg.carry_covl != 0 && (big || (small && half && (ctx->dbg.carry_covl & 2) == 0));
-    };
+    // (... and takes a COVL variant of the carry kernel — settle_carry decides it, from the same predictions)
+    const uint32_t ns_final = ctx->force_slices ? std::min<uint32_t>(ctx->force_slices, CR_MAX_SLICES_HOST) : cp.n_slices;
     // Measured (profiles/r06_experiments.txt, r6n-r6v): the 4K scene (135 heavy rows, a CU each) runs + carry 112.8 -> 94.1 us, frames/s per
     // call +3.9 %, three slots +3.8 %; the 8K triangle scene (512 light rows, two workgroups per CU) 72 -> 73 us — the head counts are one
     // more dependent round trip at the start of k_carry_rows, and with every workgroup of a full chip asking at once that costs what
@@ -585,26 +576,48 @@ int run_paint(forma_hip_ctx* ctx, DevCount nc, const PaintArgs& a, bool timing, 
     // Sweep of the switch over 4 scene families x 5 canvases x 1 / 3 slots (profiles/r06_policy_sweep_blk.json): heavy rows gain at every
     // canvas, also with two rounds of row workgroups (the 30 000-layer scene at 8192 x 8192: +3.9 %); light rows gain up to 4K (+4 %) and lose
     // 0-2 % at 8192 x 8192.
-    const bool blk = bound_j != 0 && n > 0 && !chain && covl_choice(ns_final) && n <= 0x3FFFFFFFull &&
-                     (ctx->dbg.runs_blk < 0 ? (RUNS_BLK_DEFAULT != 0 && (rows_painted <= (uint32_t)ctx->n_cus || !(small && half))) : ctx->dbg.runs_blk != 0);
+    cp.blk = bound_j != 0 && n > 0 && !cp.chain && covl_choice(ctx, cp, ns_final, bound_j != 0) && n <= 0x3FFFFFFFull &&
+             (ctx->dbg.runs_blk < 0 ? (RUNS_BLK_DEFAULT != 0 && (cp.rows_painted <= (uint32_t)ctx->n_cus || !(cp.small && cp.half))) : ctx->dbg.runs_blk != 0);
+    return cp;
+}
+// a synchronous frame after its count: the heaviest painted row is known
+void replan_carry(forma_hip_ctx* ctx, CarryPlan* cp, uint32_t max_row) {
+    ctx->pred_max_row = max_row;
+    cp->local_sort = cp->local_sort && max_row <= carry_rows_local_cap();
+    cp->n_slices = slices_for(256u, cp->rows_painted, max_row);
+}
+// the final slice count and the COVL choice with it, once the frame has runs
+void settle_carry(forma_hip_ctx* ctx, CarryPlan* cp, uint32_t bound_j) {
+    if (ctx->force_slices) cp->n_slices = ctx->force_slices;  // FORMA_HIP_DEBUG=carry_slices (tests: every slice count on one GPU)
+    ctx->cur_slices = cp->n_slices; ctx->cur_small = cp->small; ctx->cur_half = cp->half;
+    cp->covl = covl_choice(ctx, *cp, cp->n_slices, bound_j != 0);
+    ctx->covl_tried = cp->covl && bound_j != 0;
+}
+// The frame's runs (launch_runs) as `cp` numbers them; *jc: their count as the later stages see it, *J: as the host knows it (0: not).
+// Records, run keys and digests are sized for the RUNS, not for the segments (a run needs a segment, so N would always do: 440 MB of
+// records per frame slot on the 4K scene, for 21 MB of runs).  A read-back-free frame has its bound from the last verified frame; a
+// synchronous one launches the counting kernel, reads the count and sizes the buffers before the kernel that fills them.
+int number_runs(forma_hip_ctx* ctx, DevCount nc, const PaintArgs& a, const FrameTables& tab, uint32_t bound_j, bool tables_zero,
+                CarryPlan* cp, DevCount* jc, uint32_t* J) {
+    const size_t n = nc.bound;
+    const uint32_t tiles_w = a.tiles_w(), tiles_h = a.tiles_h();
+    const bool chain = cp->chain, blk = cp->blk;
+    FrameInfo* dinfo = ctx->info.as<FrameInfo>();
+    *J = 0;
     if (bound_j) {
-        jc = chain ? DevCount{nullptr, (uint32_t)n} : (blk ? DevCount{nullptr, bound_j} : DevCount{&dinfo->n_runs, bound_j});   // (chain: run indices are segment indices; blk: dense, counted by nobody before the tail)
-        if (chain || blk) { ctx->chain_rows = row_count; ctx->n_chain_rows = tiles_h; }
+        *jc = chain ? DevCount{nullptr, (uint32_t)n} : (blk ? DevCount{nullptr, bound_j} : DevCount{&dinfo->n_runs, bound_j});   // (chain: run indices are segment indices; blk: dense, counted by nobody before the tail)
+        if (chain || blk) { ctx->chain_rows = tab.row_count; ctx->n_chain_rows = tiles_h; }
     }
-    // Records, run keys and digests are sized for the RUNS, not for the segments (a run needs a segment, so N would always do:
-    // 440 MB of records per frame slot on the 4K scene, for 21 MB of runs).  A read-back-free frame has its bound from the last
-    // verified frame; a synchronous one launches the counting kernel, reads the count and sizes the buffers before the kernel
-    // that fills them.
     size_t cap = std::max<size_t>(chain ? n : bound_j, 1);
     auto runs = [&](int what) {
         launch_runs(ctx->stream, ctx->sorted, nc, tiles_w, tiles_h, blk ? ctx->rec_sp.as<TileRecord>() : ctx->records.as<TileRecord>(), (uint32_t)(blk ? n : cap),
-                    ctx->rk_u.as<uint64_t>(), tile_first_run, ctx->blk_edge.as<BlkEdge>(), row_count,
+                    ctx->rk_u.as<uint64_t>(), ctx->blk_edge.as<BlkEdge>(), tab,
                     ctx->runs_scratch.as<uint32_t>(), dinfo, /*verify_plan=*/bound_j != 0 && ctx->speculated, ctx->live44,
                     ctx->layer_sorted, ctx->pending_masks,
                     RunStyle{ctx->layer_sf.as<uint32_t>(), (uint32_t)ctx->n_orders,
                              (a.cache_id >= 0 && ctx->have_unchanged) ? ctx->unchanged.as<uint8_t>() : nullptr,
                              blk ? ctx->run_lt_sp.as<uint32_t>() : ctx->run_lt.as<uint32_t>()},
-                    tables_zero, ctx->sort_range, ctx->sort_range_n, what, chain ? row_base : (blk ? ctx->row_sp.as<uint32_t>() : nullptr), chain_zero, blk);
+                    tables_zero, ctx->sort_range, ctx->sort_range_n, what, chain ? tab.row_base : (blk ? ctx->row_sp.as<uint32_t>() : nullptr), cp->chain_zero, blk);
     };
     if (!bound_j && n > 0) {
         runs(1);
@@ -633,84 +646,66 @@ int run_paint(forma_hip_ctx* ctx, DevCount nc, const PaintArgs& a, bool timing, 
     ctx->sort_range = nullptr;
     ctx->pending_masks = PendingMasks{nullptr, 0u};
     HIPCHECK(hipGetLastError());
-    if (!bound_j) {
-        if (n > 0) {
-            HIPCHECK(hipMemcpyAsync(ctx->h_rows, row_count, (size_t)tiles_h * 4, hipMemcpyDeviceToHost, ctx->stream));
-            int rc = read_info(ctx);
-            if (rc) return rc;
-            if ((rc = verify_speculation(ctx))) return rc;
-            J = ctx->h_info->n_runs;
-            uint32_t mx = 0;
-            for (uint32_t r = crow0; r < crow1; r++) mx = std::max(mx, ctx->h_rows[r]);      // (rows that are not painted get no workgroup)
-            ctx->pred_max_row = mx;
-            local_sort = local_sort && mx <= carry_rows_local_cap();
-            n_slices = slices_for(256u, mx);
-        }
-        jc = DevCount{nullptr, J};
+    if (bound_j) return FORMA_OK;
+    if (n > 0) {
+        HIPCHECK(hipMemcpyAsync(ctx->h_rows, tab.row_count, (size_t)tiles_h * 4, hipMemcpyDeviceToHost, ctx->stream));
+        int rc = read_info(ctx);
+        if (rc) return rc;
+        if ((rc = verify_speculation(ctx))) return rc;
+        *J = ctx->h_info->n_runs;
+        const TileRect crop = crop_tiles(a);
+        uint32_t mx = 0;
+        for (uint32_t r = crop.y0; r < crop.y1; r++) mx = std::max(mx, ctx->h_rows[r]);      // (rows that are not painted get no workgroup)
+        replan_carry(ctx, cp, mx);
     }
-    bool fold_equals_paint = true;
-    for (int i = 0; i < 4; i++) {
-        uint8_t sel = a.channels[i];
-        if (sel == FORMA_CH_ALPHA && a.clear[3] == 1.0f) sel = FORMA_CH_ONE;          // renderer.rs:85-92
-        const bool colour = sel == FORMA_CH_RED || sel == FORMA_CH_GREEN || sel == FORMA_CH_BLUE;
-        if (i < 3 ? sel == FORMA_CH_ALPHA : colour) fold_equals_paint = false;
-    }
-    SpanGroups groups{nullptr, nullptr, 0u, 0u};
-    const uint32_t n_groups = (tiles_w + SPAN_GROUP_TILES - 1u) >> SPAN_GROUP_SHIFT;
-    const uint64_t* sorted_keys = ctx->rk_u.as<uint64_t>();
-    if (jc.bound > 0) {
-        const size_t jb = jc.bound;
-        HIPCHECK(ctx->span_key.ensure(jb * 8));
-        HIPCHECK(ctx->span_cov.ensure(jb * 16));
-        // (a frame whose rows hold few spans skips them altogether — the painters would load a table to learn "none": +10 us
-        //  on the 8192 x 8192 triangle scene; the first frame of a geometry does not know and goes without)
-        if (!ctx->no_span_groups && (ctx->force_span_groups || ctx->pred_row_spans > SPAN_GROUP_MIN_ROW)) {
-            // the row's spans again by tile-column group: a pool of two entries per run (a span has a run to its left, and spans
-            // longer than a group are the exception); a slice of a row that does not fit keeps only its row list
-            const size_t pool = std::min<size_t>(2 * jb, 0xFFFFFFFFu);
-            HIPCHECK(ctx->grp_tab.ensure((size_t)tiles_h * CR_MAX_SLICES_HOST * n_groups * sizeof(uint2)));
-            HIPCHECK(ctx->grp_list.ensure(pool * sizeof(uint4)));
-            groups = SpanGroups{ctx->grp_tab.as<uint2>(), ctx->grp_list.as<uint4>(), (uint32_t)pool, ctx->force_span_groups ? 0u : SPAN_GROUP_MIN_ROW};
-        }
-        if (!local_sort) {
-            HIPCHECK(ctx->rk_a.ensure(jb * 8));
-            HIPCHECK(ctx->rk_b.ensure(jb * 8));
-            HIPCHECK(ctx->sort_counters.ensure(sort_scratch_words(jb) * 4));
-            // (tile_y, layer) order: stable radix sort on bits 32..63 = [layer 21 | tile_y+1 11]; live bits come from the
-            // rasterizer's varying-bit mask (layer = key bits 0..20, tile_y = key bits 33..43)
-            uint64_t live = ((ctx->live44 & 0x1FFFFFull) | ((ctx->live44 >> 33) << 21)) << 32;
-            const SortPlan rk_plan = make_sort_plan(live, 32, 64, ctx->digit_bits);
-            sorted_keys = launch_radix_sort(ctx->stream, ctx->rk_u.as<uint64_t>(), ctx->rk_a.as<uint64_t>(),
-                                            ctx->rk_b.as<uint64_t>(), jc, rk_plan, ctx->digit_bits,
-                                            ctx->sort_counters.as<uint32_t>(), &dinfo->error, nullptr, nullptr);
-            ctx->pz.sort_p = nullptr;
-        }
-        if (ctx->force_slices) n_slices = ctx->force_slices;  // FORMA_HIP_DEBUG=carry_slices (tests: every slice count on one GPU)
-        ctx->cur_slices = n_slices; ctx->cur_small = small; ctx->cur_half = half;
-        // COVL (paint.hip): a row in ONE slice whose runs fit carry_rows_covl_cap() — the 4K scene's 4 800 — stages its cover sums
-        // and style summaries in LDS before the walk.  A read-back-free frame guesses from the last verified frame's heaviest row
-        // (6 % head-room); a row beyond the cap voids the frame and the synchronous re-run knows the rows.
-        {
-            // (the 512-lane variant for light rows in one slice — the 8K triangle scene — has the room as well: 32 KB of covers, two
-            //  workgroups per CU instead of three, still one round for 512 rows)
-            covl = covl_choice(n_slices);
-            ctx->covl_tried = covl && bound_j != 0;
-        }
-    } else {
+    *jc = DevCount{nullptr, *J};
+    return FORMA_OK;
+}
+// span records, the tile-column group lists (*groups) and — rows not ordered in LDS — the global run sort (*sorted_keys: its output)
+int provision_spans(forma_hip_ctx* ctx, DevCount jc, uint32_t tiles_w, uint32_t tiles_h, bool local_sort, SpanGroups* groups,
+                    const uint64_t** sorted_keys) {
+    *groups = SpanGroups{nullptr, nullptr, 0u, 0u};
+    *sorted_keys = ctx->rk_u.as<uint64_t>();
+    if (jc.bound == 0) {
         HIPCHECK(ctx->span_key.ensure(8));
         HIPCHECK(ctx->span_cov.ensure(16));
+        return FORMA_OK;
     }
-    ctx->image_sent = false;
-    uint32_t bin_shift = 0;                               // 256 layer bins over the orders in use
-    while (bin_shift < 16 && (((uint64_t)std::max<size_t>(ctx->n_orders, 1) - 1) >> bin_shift) > 255) bin_shift++;
-
-    PaintParams P;
-    P.width = a.width; P.height = a.height; P.tiles_w = tiles_w; P.tiles_h = tiles_h;
-    P.crop_x0 = 0; P.crop_x1 = tiles_w; P.crop_y0 = 0; P.crop_y1 = tiles_h;
-    if (a.crop) {                                         // Rect::new, renderer.rs:43-52
-        P.crop_x0 = a.crop->x0 / 16; P.crop_x1 = std::min(tiles_w, (a.crop->x1 + 15) / 16);
-        P.crop_y0 = a.crop->y0 / 16; P.crop_y1 = std::min(tiles_h, (a.crop->y1 + 15) / 16);
+    const size_t jb = jc.bound;
+    HIPCHECK(ctx->span_key.ensure(jb * 8));
+    HIPCHECK(ctx->span_cov.ensure(jb * 16));
+    // (a frame whose rows hold few spans skips them altogether — the painters would load a table to learn "none": +10 us
+    //  on the 8192 x 8192 triangle scene; the first frame of a geometry does not know and goes without)
+    if (!ctx->no_span_groups && (ctx->force_span_groups || ctx->pred_row_spans > SPAN_GROUP_MIN_ROW)) {
+        // the row's spans again by tile-column group: a pool of two entries per run (a span has a run to its left, and spans
+        // longer than a group are the exception); a slice of a row that does not fit keeps only its row list
+        const uint32_t n_groups = (tiles_w + SPAN_GROUP_TILES - 1u) >> SPAN_GROUP_SHIFT;
+        const size_t pool = std::min<size_t>(2 * jb, 0xFFFFFFFFu);
+        HIPCHECK(ctx->grp_tab.ensure((size_t)tiles_h * CR_MAX_SLICES_HOST * n_groups * sizeof(uint2)));
+        HIPCHECK(ctx->grp_list.ensure(pool * sizeof(uint4)));
+        *groups = SpanGroups{ctx->grp_tab.as<uint2>(), ctx->grp_list.as<uint4>(), (uint32_t)pool, ctx->force_span_groups ? 0u : SPAN_GROUP_MIN_ROW};
     }
+    if (!local_sort) {
+        HIPCHECK(ctx->rk_a.ensure(jb * 8));
+        HIPCHECK(ctx->rk_b.ensure(jb * 8));
+        HIPCHECK(ctx->sort_counters.ensure(sort_scratch_words(jb) * 4));
+        // (tile_y, layer) order: stable radix sort on bits 32..63 = [layer 21 | tile_y+1 11]; live bits come from the
+        // rasterizer's varying-bit mask (layer = key bits 0..20, tile_y = key bits 33..43)
+        uint64_t live = ((ctx->live44 & 0x1FFFFFull) | ((ctx->live44 >> 33) << 21)) << 32;
+        const SortPlan rk_plan = make_sort_plan(live, 32, 64, ctx->digit_bits);
+        *sorted_keys = launch_radix_sort(ctx->stream, ctx->rk_u.as<uint64_t>(), ctx->rk_a.as<uint64_t>(),
+                                         ctx->rk_b.as<uint64_t>(), jc, rk_plan, ctx->digit_bits,
+                                         ctx->sort_counters.as<uint32_t>(), &ctx->info.as<FrameInfo>()->error, nullptr, nullptr);
+        ctx->pz.sort_p = nullptr;
+    }
+    return FORMA_OK;
+}
+// the painters' parameters with the heavy-first order off; rows: the tile tables of runs numbered per tile row or per tile, else nullptr
+PaintParams paint_params(const forma_hip_ctx* ctx, const PaintArgs& a, uint32_t clear_unchanged, uint32_t n_slices, const FrameTables* rows) {
+    PaintParams P{};
+    const TileRect crop = crop_tiles(a);
+    P.width = a.width; P.height = a.height; P.tiles_w = a.tiles_w(); P.tiles_h = a.tiles_h();
+    P.crop_x0 = crop.x0; P.crop_x1 = crop.x1; P.crop_y0 = crop.y0; P.crop_y1 = crop.y1;
     uint8_t ch[4] = {a.channels[0], a.channels[1], a.channels[2], a.channels[3]};
     if (a.clear[3] == 1.0f)                               // renderer.rs:85-92: Alpha -> One when clear is opaque
         for (int i = 0; i < 4; i++) if (ch[i] == FORMA_CH_ALPHA) ch[i] = FORMA_CH_ONE;
@@ -718,111 +713,154 @@ int run_paint(forma_hip_ctx* ctx, DevCount nc, const PaintArgs& a, bool timing, 
     for (int i = 0; i < 4; i++) P.clear[i] = a.clear[i];
     P.stride_px = a.target ? (uint32_t)(a.target_pitch / (a.fmt == FORMA_FORMAT_LINEAR_F16 ? 8u : 4u)) : a.width; P.scene_has_clips = ctx->scene_has_clips ? 1u : 0u; P.scene_simple = ctx->scene_simple ? 1u : 0u; P.n_orders = (uint32_t)ctx->n_orders; P.n_words = (uint32_t)ctx->n_words;
     P.clear_unchanged = clear_unchanged;
-    P.n_slices = jc.bound > 0 ? n_slices : 1u;             // (no runs: the carry pre-pass did not run, the zeroed tables say "no spans")
-    P.n_groups = n_groups;
+    P.n_slices = n_slices;
+    P.n_groups = (P.tiles_w + SPAN_GROUP_TILES - 1u) >> SPAN_GROUP_SHIFT;
     // occlusion culling (PaintParams::cull): not with a buffer-layer cache (a tile's layer count is state there), not with clips
     // ... and only for a geometry whose tiles have been seen to overflow the wave painter's lists (k_paint_deep ran): that is where
     // culling pays — 1080p cubics: painter 85 -> 24 us — while a scene of moderate lists (the 4K stand-in: 39 entries per tile,
     // phases bound by their dependent steps, not by the entries) only pays for the occluder scan, ~1 % of its frames/s.
-    const bool cull = a.cache_id < 0 && !ctx->scene_has_clips && !ctx->dbg.no_cull && (ctx->cull_on || ctx->dbg.force_cull);
-    P.cull = cull ? 1u : 0u;
-    // heaviest tiles first (PaintParams::order_*): read-back-free frames without a cache, one wavefront per tile
-    P.order_cnt_in = nullptr; P.order_list_in = nullptr; P.order_cnt_out = nullptr; P.order_list_out = nullptr;
-    P.row_base = (chain || blk) ? row_base : nullptr; P.row_cnt = (chain || blk) ? row_count : nullptr;
+    P.cull = a.cache_id < 0 && !ctx->scene_has_clips && !ctx->dbg.no_cull && (ctx->cull_on || ctx->dbg.force_cull) ? 1u : 0u;
+    P.row_base = rows ? rows->row_base : nullptr; P.row_cnt = rows ? rows->row_count : nullptr;
+    return P;
+}
+// heaviest tiles first (PaintParams::order_*): read-back-free frames without a cache, one wavefront per tile
+int heavy_order(forma_hip_ctx* ctx, const PaintArgs& a, uint32_t bound_j, DevCount jc, const FrameTables& tab, uint32_t tiles_painted,
+                bool strips, bool quads, int split_n, PaintParams* P) {
     ctx->order_pending = -1; ctx->order_cnt_dev = nullptr; ctx->order_keep_dev = nullptr;
-    const uint32_t tiles_painted = (P.crop_y1 > P.crop_y0 ? P.crop_y1 - P.crop_y0 : 0u) * tiles_w;
-    const bool strips = paint_by_strips(ctx, tiles_painted);
-    const bool quads = paint_by_quads(ctx, a.cache_id, chain ? bound_j : jc.bound, tiles_painted);   // (k_paint_quad ignores order_*)
-    P.order_flag_in = nullptr; P.order_flag_out = nullptr; P.order_hcap = 0; P.order_thr = 0;
     if (ctx->dbg.order_thr >= 0) ctx->order_off = 0;
     if (ctx->order_off) ctx->order_off--;                 // (a flat scene: the order is retried every 256 frames)
     // ... of launches that are a handful of rounds of wavefronts: one tile's life is then a good part of the launch's.  A frame
     // of 32 rounds (the 8K scene: 262 144 tiles on 8 192 wave slots) has no tail worth 10 % of bookkeeping.
-    // a frame that leaves in bands (split_plan below) paints in several launches: no heavy-first order across them
+    if (!(ctx->order_enable && bound_j && a.cache_id < 0 && !strips && !quads && !ctx->dbg.no_order && jc.bound > 0 && tiles_painted && !ctx->order_off && split_n == 0 &&
+          tiles_painted <= 16u * paint_strip_tiles(ctx) && (one_frame_in_flight(ctx) || ctx->dbg.order_thr >= 0))) { ctx->order_cur = -1; return FORMA_OK; }   // (any other frame in between: the lists are stale)
+    // (heavy section: an eighth of the band's tiles, as PAINT_ORDER_SUBS lists of equal capacity)
+    const size_t per = paint_band_tiles(P->crop_y1 > P->crop_y0 ? P->crop_y1 - P->crop_y0 : 0u, P->tiles_w), hcap = std::max<size_t>((per / 8 + PAINT_ORDER_SUBS - 1) / PAINT_ORDER_SUBS, 2) * PAINT_ORDER_SUBS;
+    const size_t set_words = PAINT_ORDER_WORDS + 8 * hcap + (8 * per + 3) / 4;      // counts | lists | one flag byte per tile
+    if (ctx->order_buf.cap < 2 * set_words * 4) {
+        HIPCHECK(ctx->order_buf.ensure(2 * set_words * 4));
+        HIPCHECK(hipMemsetAsync(ctx->order_buf.p, 0, ctx->order_buf.cap, ctx->stream));   // (flag bytes nobody has written yet say "not heavy")
+        ctx->order_cur = -1;
+    }
+    const forma_hip_ctx::OrderSig sig{P->tiles_w, P->tiles_h, P->crop_x0, P->crop_x1, P->crop_y0, P->crop_y1};
+    uint32_t* base = ctx->order_buf.as<uint32_t>();
+    if (ctx->order_cur >= 0 && !(ctx->order_sig == sig)) ctx->order_cur = -1;
+    const int w = ctx->order_cur == 0 ? 1 : 0;
+    if (ctx->order_cur >= 0) {
+        P->order_cnt_in = base + (size_t)ctx->order_cur * set_words; P->order_list_in = P->order_cnt_in + PAINT_ORDER_WORDS;
+        P->order_flag_in = reinterpret_cast<const uint8_t*>(P->order_list_in + 8 * hcap);
+    }
+    uint32_t* wset = base + (size_t)w * set_words;
+    P->order_cnt_out = tab.order_cnt; P->order_list_out = wset + PAINT_ORDER_WORDS;
+    P->order_flag_out = reinterpret_cast<uint8_t*>(wset + PAINT_ORDER_WORDS + 8 * hcap);
+    P->order_hcap = (uint32_t)hcap; P->order_thr = ctx->dbg.order_thr >= 0 ? (uint32_t)ctx->dbg.order_thr : ctx->order_thr;
+    ctx->order_pending = w; ctx->order_pending_sig = sig; ctx->order_tiles = tiles_painted;
+    ctx->order_cnt_dev = tab.order_cnt; ctx->order_keep_dev = wset;
+    return FORMA_OK;
+}
+// the carry pre-pass as `cp` planned it
+void launch_carry(forma_hip_ctx* ctx, const PaintArgs& a, const PaintParams& P, const FrameTables& tab, const CarryPlan& cp,
+                  DevCount nc, DevCount jc, SpanGroups groups, const uint64_t* sorted_keys) {
+    bool fold_equals_paint = true;
+    for (int i = 0; i < 4; i++) {
+        const uint32_t sel = (P.channels >> (8 * i)) & 0xFFu;                         // (Alpha -> One when clear is opaque: renderer.rs:85-92)
+        const bool colour = sel == FORMA_CH_RED || sel == FORMA_CH_GREEN || sel == FORMA_CH_BLUE;
+        if (i < 3 ? sel == FORMA_CH_ALPHA : colour) fold_equals_paint = false;
+    }
+    uint32_t bin_shift = 0;                               // 256 layer bins over the orders in use
+    while (bin_shift < 16 && (((uint64_t)std::max<size_t>(ctx->n_orders, 1) - 1) >> bin_shift) > 255) bin_shift++;
+    launch_carry_rows(ctx->stream, cp.local_sort, cp.small, cp.half, cp.n_slices, bin_shift, sorted_keys, ctx->records.as<TileRecord>(),
+                      ctx->blk_edge.as<BlkEdge>(), nc, jc, ctx->layer_sf.as<uint32_t>(),
+                      (uint32_t)ctx->n_orders, P.tiles_w, P.tiles_h, tab.row_count, tab.row_span_lo,
+                      tab.row_span_cnt, ctx->span_key.as<uint64_t>(), ctx->span_cov.as<uint4>(),
+                      (a.cache_id >= 0 && ctx->have_unchanged) ? ctx->unchanged.as<uint8_t>() : nullptr, ctx->info.as<FrameInfo>(),
+                      runs_edge_segments(),
+                      // invisible carries of a partial last tile row are dropped only when nothing can observe them: with a
+                      // buffer-layer cache the layer count of a tile is state (passes/tile_unchanged.rs)
+                      // ... nor when the channel order tells a folded tile from a painted one: the solid fold encodes output
+                      // bytes 0..2 as sRGB and passes byte 3 through (to_srgb_bytes of the SELECTED channels, painter/mod.rs:
+                      // 156-162, 692), a painted tile encodes r, g, b and then selects (compute_srgb, :466-483) — the same bytes
+                      // unless alpha lands in bytes 0..2 or a colour in byte 3, and an invisible layer can block the fold
+                      (a.cache_id < 0 && (a.height & 15u) && fold_equals_paint) ? (a.height & 15u) : 16u, P.crop_y0, P.crop_y1, groups, ctx->run_lt.as<uint32_t>(),
+                      P.cull != 0,
+                      (a.cache_id >= 0 || !fold_equals_paint) ? P.crop_x0 : 0xFFFFFFFFu,
+                      cp.chain ? tab.row_base : nullptr, cp.covl,
+                      cp.blk ? BlkRuns{ctx->rec_sp.as<TileRecord>(), ctx->run_lt_sp.as<uint32_t>(), ctx->runs_scratch.as<uint32_t>(),
+                                       ctx->row_sp.as<uint32_t>(), tab.row_base, tab.tile_first_run, ctx->run_lt.as<uint32_t>(),
+                                       (uint32_t)ctx->dbg.blk_round}
+                             : BlkRuns{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 256u});
+}
+// what the painters of the frame run_paint enqueued read (finish_paint asks again: the same pointers)
+PaintInputs paint_inputs(forma_hip_ctx* ctx, const FrameTables& tab, DevCount jc, TileCacheArgs tc) {
+    return PaintInputs{ctx->sorted, ctx->records.as<TileRecord>(), jc, tab.tile_first_run, tab.row_span_lo, tab.row_span_cnt,
+                       ctx->span_key.as<uint64_t>(), ctx->span_cov.as<uint4>(), ctx->layer_col.as<uint4>(), ctx->style_off.as<uint32_t>(),
+                       ctx->style_words.as<uint32_t>(), ctx->images.as<forma_image_t>(), ctx->texels.as<uint16_t>(), ctx->cur_image, tc,
+                       ctx->info.as<FrameInfo>()};
+}
+
+// stage 4 on ctx->sorted (n segments): runs + carry pre-pass + per-tile painter -> ctx->image
+// bound_j != 0: asynchronous — the run count stays on the device (info->n_runs), buffers are provisioned for bound_j runs.
+int run_paint(forma_hip_ctx* ctx, DevCount nc, const PaintArgs& a, bool timing, uint32_t bound_j = 0) {
+    const size_t n = nc.bound;
+    // set_styles and set_images are separate calls: the image a texture style names is checked where both are known
+    if (ctx->any_texture && ctx->max_image_index >= ctx->n_images) return fail(ctx, FORMA_E_ARG, "texture style names an image that was not uploaded");
+    const uint32_t tiles_w = a.tiles_w(), tiles_h = a.tiles_h();
+    ctx->img_w = a.width; ctx->img_h = a.height;
+    ctx->chain_rows = nullptr; ctx->n_chain_rows = 0;
+    int rc; PaintTarget tg;
+    if ((rc = paint_target(ctx, a, &tg))) return rc;
+    HIPCHECK(ctx->row_tab.ensure(frame_tables(nullptr, tiles_w, tiles_h).total_words * 4));
+    const FrameTables tab = frame_tables(ctx->row_tab.as<uint32_t>(), tiles_w, tiles_h);
+    HIPCHECK(ctx->blk_edge.ensure(runs_blocks(std::max<size_t>(n, 1)) * sizeof(BlkEdge)));
+    HIPCHECK(ctx->runs_scratch.ensure(runs_scratch_words(std::max<size_t>(n, 1)) * 4));
+    stage_begin(ctx, ST_CARRY, timing);
+    const bool tables_zero = ctx->pz.tab_p == ctx->row_tab.p && ctx->pz.tab_words >= tab.zero_words;
+    ctx->pz.tab_p = nullptr;
+    CarryPlan cp = plan_carry(ctx, a, n, bound_j);
+    DevCount jc; uint32_t J;
+    if ((rc = number_runs(ctx, nc, a, tab, bound_j, tables_zero, &cp, &jc, &J))) return rc;
+    SpanGroups groups; const uint64_t* sorted_keys;
+    if ((rc = provision_spans(ctx, jc, tiles_w, tiles_h, cp.local_sort, &groups, &sorted_keys))) return rc;
+    if (jc.bound > 0) settle_carry(ctx, &cp, bound_j);
+    ctx->image_sent = false;
+    // (no runs: the carry pre-pass does not run, the zeroed tables say "no spans")
+    PaintParams P = paint_params(ctx, a, tg.clear_unchanged, jc.bound > 0 ? cp.n_slices : 1u, cp.chain || cp.blk ? &tab : nullptr);
+    const uint32_t tiles_painted = (P.crop_y1 > P.crop_y0 ? P.crop_y1 - P.crop_y0 : 0u) * tiles_w;
+    const bool strips = paint_by_strips(ctx, tiles_painted);
+    const bool quads = paint_by_quads(ctx, a.cache_id, cp.chain ? bound_j : jc.bound, tiles_painted);   // (k_paint_quad ignores order_*)
+    // a frame that leaves in bands paints in several launches: no heavy-first order across them
+    // (split_plan runs before launch_deep is known, which may drop the split below: ADVICE.md, third finding)
     const int split_n = split_plan(ctx, a, P, bound_j, timing);
-    if (ctx->order_enable && bound_j && a.cache_id < 0 && !strips && !quads && !ctx->dbg.no_order && jc.bound > 0 && tiles_painted && !ctx->order_off && split_n == 0 &&
-        tiles_painted <= 16u * paint_strip_tiles(ctx) && (one_frame_in_flight(ctx) || ctx->dbg.order_thr >= 0)) {
-        // (heavy section: an eighth of the band's tiles, as PAINT_ORDER_SUBS lists of equal capacity)
-        const size_t per = paint_band_tiles(P.crop_y1 > P.crop_y0 ? P.crop_y1 - P.crop_y0 : 0u, tiles_w), hcap = std::max<size_t>((per / 8 + PAINT_ORDER_SUBS - 1) / PAINT_ORDER_SUBS, 2) * PAINT_ORDER_SUBS;
-        const size_t set_words = PAINT_ORDER_WORDS + 8 * hcap + (8 * per + 3) / 4;      // counts | lists | one flag byte per tile
-        if (ctx->order_buf.cap < 2 * set_words * 4) {
-            HIPCHECK(ctx->order_buf.ensure(2 * set_words * 4));
-            HIPCHECK(hipMemsetAsync(ctx->order_buf.p, 0, ctx->order_buf.cap, ctx->stream));   // (flag bytes nobody has written yet say "not heavy")
-            ctx->order_cur = -1;
-        }
-        const forma_hip_ctx::OrderSig sig{tiles_w, tiles_h, P.crop_x0, P.crop_x1, P.crop_y0, P.crop_y1};
-        uint32_t* base = ctx->order_buf.as<uint32_t>();
-        if (ctx->order_cur >= 0 && !(ctx->order_sig == sig)) ctx->order_cur = -1;
-        const int w = ctx->order_cur == 0 ? 1 : 0;
-        if (ctx->order_cur >= 0) {
-            P.order_cnt_in = base + (size_t)ctx->order_cur * set_words; P.order_list_in = P.order_cnt_in + PAINT_ORDER_WORDS;
-            P.order_flag_in = reinterpret_cast<const uint8_t*>(P.order_list_in + 8 * hcap);
-        }
-        uint32_t* wset = base + (size_t)w * set_words;
-        P.order_cnt_out = order_cnt; P.order_list_out = wset + PAINT_ORDER_WORDS;
-        P.order_flag_out = reinterpret_cast<uint8_t*>(wset + PAINT_ORDER_WORDS + 8 * hcap);
-        P.order_hcap = (uint32_t)hcap; P.order_thr = ctx->dbg.order_thr >= 0 ? (uint32_t)ctx->dbg.order_thr : ctx->order_thr;
-        ctx->order_pending = w; ctx->order_pending_sig = sig; ctx->order_tiles = tiles_painted;
-        ctx->order_cnt_dev = order_cnt; ctx->order_keep_dev = wset;
-    } else ctx->order_cur = -1;                              // (any other frame in between: the lists are stale)
+    if ((rc = heavy_order(ctx, a, bound_j, jc, tab, tiles_painted, strips, quads, split_n, &P))) return rc;
     // the (empty) k_paint_deep launch costs ~5 us of every frame: a read-back-free frame without a cache skips it when the
     // last verified frame had no deep tile; a tile that needs it then voids the frame (re-run in full)
     const bool launch_deep = !(bound_j != 0 && a.cache_id < 0 && ctx->pred_no_deep);
-    if (jc.bound > 0)
-        launch_carry_rows(ctx->stream, local_sort, small, half, n_slices, bin_shift, sorted_keys, ctx->records.as<TileRecord>(),
-                          ctx->blk_edge.as<BlkEdge>(), nc, jc, ctx->layer_sf.as<uint32_t>(),
-                          (uint32_t)ctx->n_orders, tiles_w, tiles_h, row_count, row_span_lo,
-                          row_span_cnt, ctx->span_key.as<uint64_t>(), ctx->span_cov.as<uint4>(),
-                          (a.cache_id >= 0 && ctx->have_unchanged) ? ctx->unchanged.as<uint8_t>() : nullptr, dinfo,
-                          runs_edge_segments(),
-                          // invisible carries of a partial last tile row are dropped only when nothing can observe them: with a
-                          // buffer-layer cache the layer count of a tile is state (passes/tile_unchanged.rs)
-                          // ... nor when the channel order tells a folded tile from a painted one: the solid fold encodes output
-                          // bytes 0..2 as sRGB and passes byte 3 through (to_srgb_bytes of the SELECTED channels, painter/mod.rs:
-                          // 156-162, 692), a painted tile encodes r, g, b and then selects (compute_srgb, :466-483) — the same bytes
-                          // unless alpha lands in bytes 0..2 or a colour in byte 3, and an invisible layer can block the fold
-                          (a.cache_id < 0 && (a.height & 15u) && fold_equals_paint) ? (a.height & 15u) : 16u, crow0, crow1, groups, ctx->run_lt.as<uint32_t>(),
-                          cull,
-                          (a.cache_id >= 0 || !fold_equals_paint) ? (a.crop ? a.crop->x0 / 16 : 0u) : 0xFFFFFFFFu,
-                          chain ? row_base : nullptr, covl,
-                          blk ? BlkRuns{ctx->rec_sp.as<TileRecord>(), ctx->run_lt_sp.as<uint32_t>(), ctx->runs_scratch.as<uint32_t>(),
-                                        ctx->row_sp.as<uint32_t>(), row_base, tile_first_run, ctx->run_lt.as<uint32_t>(),
-                                        (uint32_t)ctx->dbg.blk_round}
-                              : BlkRuns{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 256u});
+    if (jc.bound > 0) launch_carry(ctx, a, P, tab, cp, nc, jc, groups, sorted_keys);
     stage_end(ctx, ST_CARRY, timing);
     stage_begin(ctx, ST_PAINT, timing);
+    // the painter in bands of tile rows, an event behind each (render_on sends their pixels out behind those) — or as one band
+    const int bands = split_n > 1 && !launch_deep ? split_n : 1;
     ctx->split_n = 0;
-    if (split_n > 1 && !launch_deep) {
-        // the painter in bands of tile rows, an event behind each: render_on sends the bands' pixels out behind those events
+    ctx->split_row[0] = P.crop_y0; ctx->split_row[bands] = P.crop_y1;
+    if (bands > 1) {
         const uint32_t rows = P.crop_y1 - P.crop_y0;
-        for (int k = 0; k <= split_n; k++) ctx->split_row[k] = P.crop_y0 + (uint32_t)((uint64_t)rows * (uint32_t)k / (uint32_t)split_n);
+        for (int k = 1; k < bands; k++) ctx->split_row[k] = P.crop_y0 + (uint32_t)((uint64_t)rows * (uint32_t)k / (uint32_t)bands);
         // the policy's two bands: the first a quarter of the rows (split_first) — its copy must last until the rest is painted, or
         // the link idles between the two (10 %: slower than one launch; 22-30 %: the plateau; profiles/r06_experiments.txt, r8g)
-        if (split_n == 2) ctx->split_row[1] = P.crop_y0 + std::min(std::max(rows * (uint32_t)ctx->dbg.split_first / 100u, 1u), rows - 1u);
-        for (int k = 0; k < split_n; k++) {
-            PaintParams Pk = P;
-            Pk.crop_y0 = ctx->split_row[k]; Pk.crop_y1 = ctx->split_row[k + 1];
-            launch_paint(ctx->stream, Pk, ctx->sorted, ctx->records.as<TileRecord>(), jc, tile_first_run, row_span_lo,
-                         row_span_cnt, ctx->span_key.as<uint64_t>(), ctx->span_cov.as<uint4>(), ctx->layer_col.as<uint4>(),
-                         ctx->style_off.as<uint32_t>(),
-                         ctx->style_words.as<uint32_t>(), ctx->images.as<forma_image_t>(), ctx->texels.as<uint16_t>(),
-                         ctx->cur_image, tc, dinfo, paint_overflow, overflow_list, over2_n, over2_list, false, groups,
-                         strips, quads, mid_n, mid_list, ctx->n_cus, a.fmt);
-            HIPCHECK(hipEventRecord(ctx->split_ev[k], ctx->stream));
-        }
-        ctx->split_n = split_n;
-    } else
-    launch_paint(ctx->stream, P, ctx->sorted, ctx->records.as<TileRecord>(), jc, tile_first_run, row_span_lo,
-                 row_span_cnt, ctx->span_key.as<uint64_t>(), ctx->span_cov.as<uint4>(), ctx->layer_col.as<uint4>(),
-                 ctx->style_off.as<uint32_t>(),
-                 ctx->style_words.as<uint32_t>(), ctx->images.as<forma_image_t>(), ctx->texels.as<uint16_t>(),
-                 ctx->cur_image, tc, dinfo, paint_overflow, overflow_list, over2_n, over2_list, launch_deep, groups,
-                 strips, quads, mid_n, mid_list, ctx->n_cus, a.fmt);
+        if (bands == 2) ctx->split_row[1] = P.crop_y0 + std::min(std::max(rows * (uint32_t)ctx->dbg.split_first / 100u, 1u), rows - 1u);
+    }
+    const PaintInputs in = paint_inputs(ctx, tab, jc, tg.tc);
+    for (int k = 0; k < bands; k++) {
+        PaintParams Pk = P;
+        Pk.crop_y0 = ctx->split_row[k]; Pk.crop_y1 = ctx->split_row[k + 1];
+        launch_paint(ctx->stream, Pk, in, tab, groups, launch_deep, strips, quads, ctx->n_cus, a.fmt);
+        if (bands > 1) HIPCHECK(hipEventRecord(ctx->split_ev[k], ctx->stream));
+    }
+    if (bands > 1) ctx->split_n = bands;
     stage_end(ctx, ST_PAINT, timing);
     ctx->last_runs = J; ctx->last_entries = 0;
     HIPCHECK(hipGetLastError());
     // what a later launch_paint_huge needs (tiles deeper than the painter's LDS lists: finish_paint)
-    ctx->huge = forma_hip_ctx::HugeArgs{P, jc, tc, tile_first_run, row_span_lo, row_span_cnt, over2_n, over2_list, T, a.fmt};
+    ctx->huge = forma_hip_ctx::HugeArgs{P, jc, tg.tc, a.fmt};
     return FORMA_OK;
 }
 
@@ -833,12 +871,13 @@ int run_paint(forma_hip_ctx* ctx, DevCount nc, const PaintArgs& a, bool timing, 
 int finish_paint(forma_hip_ctx* ctx) {
     if (!(ctx->h_info->error & 8u)) return FORMA_OK;
     const forma_hip_ctx::HugeArgs& h = ctx->huge;
+    const FrameTables tab = frame_tables(ctx->row_tab.as<uint32_t>(), h.P.tiles_w, h.P.tiles_h);
     uint32_t n = 0;
-    HIPCHECK(hipMemcpyAsync(&n, h.over2_n, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHECK(hipMemcpyAsync(&n, tab.over2_n, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHECK(hipStreamSynchronize(ctx->stream));
-    n = std::min(n, h.T);
+    n = std::min(n, h.P.tiles_w * h.P.tiles_h);
     std::vector<uint32_t> list((size_t)2 * n);
-    if (n) HIPCHECK(hipMemcpy(list.data(), h.over2_list, (size_t)8 * n, hipMemcpyDeviceToHost));
+    if (n) HIPCHECK(hipMemcpy(list.data(), tab.over2_list, (size_t)8 * n, hipMemcpyDeviceToHost));
     std::vector<uint64_t> offs(n);
     uint64_t total = 0;
     for (uint32_t i = 0; i < n; i++) { offs[i] = total; total += list[2 * i + 1]; }
@@ -851,10 +890,7 @@ int finish_paint(forma_hip_ctx* ctx) {
     if (n) HIPCHECK(hipMemcpyAsync(ctx->huge_offs.p, offs.data(), (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
     // (a read-back-free frame ended with k_frame_tail: the device-side run count is back to zero — the host copy has it)
     const DevCount jc = h.jc.ptr ? DevCount{nullptr, std::min(ctx->h_info->n_runs, h.jc.bound)} : h.jc;
-    launch_paint_huge(ctx->stream, h.P, ctx->sorted, ctx->records.as<TileRecord>(), jc, h.tile_first_run, h.row_span_lo, h.row_span_cnt,
-                      ctx->span_key.as<uint64_t>(), ctx->span_cov.as<uint4>(), ctx->layer_col.as<uint4>(), ctx->style_off.as<uint32_t>(),
-                      ctx->style_words.as<uint32_t>(), ctx->images.as<forma_image_t>(), ctx->texels.as<uint16_t>(), ctx->cur_image, h.tc,
-                      ctx->info.as<FrameInfo>(), h.over2_list, n, ctx->huge_offs.as<uint64_t>(), ctx->huge_key.as<uint64_t>(),
+    launch_paint_huge(ctx->stream, h.P, paint_inputs(ctx, tab, jc, h.tc), tab, n, ctx->huge_offs.as<uint64_t>(), ctx->huge_key.as<uint64_t>(),
                       ctx->huge_tmp.as<uint64_t>(), ctx->huge_flag.as<uint32_t>(), h.fmt);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(ctx->stream));           // (`offs` is host memory of this call)
@@ -883,11 +919,9 @@ int copy_rows_out(forma_hip_ctx* ctx, hipStream_t s, uint8_t* dst, size_t stride
 // frame's kernels are enqueued — a copy into pageable memory blocks the host until it is done.
 int send_split_bands(forma_hip_ctx* ctx, uint8_t* dst, size_t stride, const PaintArgs& a) {
     if (ctx->split_n < 2 || !dst) return FORMA_OK;
-    const uint32_t tiles_w = (a.width + 15) / 16;
-    uint32_t tx0 = 0, tx1 = tiles_w;
-    if (a.crop) { tx0 = a.crop->x0 / 16; tx1 = std::min(tiles_w, (a.crop->x1 + 15) / 16); }
-    if (tx0 >= tx1) return FORMA_OK;
-    const size_t px0 = (size_t)tx0 * 16, px1 = std::min<size_t>((size_t)tx1 * 16, a.width);
+    const TileRect crop = crop_tiles(a);
+    if (crop.x0 >= crop.x1) return FORMA_OK;
+    const size_t px0 = (size_t)crop.x0 * 16, px1 = std::min<size_t>((size_t)crop.x1 * 16, a.width);
     ctx->split_sent = true;
     for (int k = 0; k < ctx->split_n; k++) {
         const size_t py0 = (size_t)ctx->split_row[k] * 16, py1 = std::min<size_t>((size_t)ctx->split_row[k + 1] * 16, a.height);
@@ -911,12 +945,8 @@ int settle_split(forma_hip_ctx* ctx) {
 // cache the tiles the painter skipped (TileWriteOp::None), keep whatever the caller's buffer holds (reference
 // cpu/buffer/layout/mod.rs:264-295 writes tile by tile; forma/src/cpu/buffer/mod.rs doc test "skipped rendering").
 int copy_image_out(forma_hip_ctx* ctx, uint8_t* dst, size_t stride, bool timing, const PaintArgs& a, bool already_there = false) {
-    const uint32_t tiles_w = (a.width + 15) / 16, tiles_h = (a.height + 15) / 16;
-    uint32_t tx0 = 0, tx1 = tiles_w, ty0 = 0, ty1 = tiles_h;
-    if (a.crop) {
-        tx0 = a.crop->x0 / 16; tx1 = std::min(tiles_w, (a.crop->x1 + 15) / 16);
-        ty0 = a.crop->y0 / 16; ty1 = std::min(tiles_h, (a.crop->y1 + 15) / 16);
-    }
+    const uint32_t tiles_w = a.tiles_w(), tiles_h = a.tiles_h();
+    const auto [tx0, tx1, ty0, ty1] = crop_tiles(a);
     ctx->last_written = 0;
     ctx->lw_valid = true; ctx->lw_tiles_w = tiles_w; ctx->lw_tiles_h = tiles_h; ctx->lw_cache = a.cache_id >= 0; ctx->lw_flags_on_host = false;
     ctx->lw_tx0 = tx0; ctx->lw_tx1 = std::max(tx0, tx1); ctx->lw_ty0 = ty0; ctx->lw_ty1 = std::max(ty0, ty1);
@@ -1172,16 +1202,8 @@ void forma_hip_destroy(forma_hip_ctx* ctx) {
     ctx->slots.clear();
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    DevBuf* all[] = {&ctx->x, &ctx->y, &ctx->line_slot, &ctx->geoms, &ctx->style_off, &ctx->style_words, &ctx->layer_sf, &ctx->layer_col, &ctx->unchanged,
-                     &ctx->images, &ctx->texels, &ctx->l_order, &ctx->l_x0, &ctx->l_y0, &ctx->l_dx, &ctx->l_dy, &ctx->l_a,
-                     &ctx->l_b, &ctx->l_c, &ctx->l_d, &ctx->l_len, &ctx->scan_tmp, &ctx->cl_idx, &ctx->cl_start,
-                     &ctx->block_first, &ctx->prep_scratch, &ctx->seg_u, &ctx->seg_a, &ctx->seg_b,
-                     &ctx->sort_counters, &ctx->info, &ctx->info_init, &ctx->records, &ctx->rk_u, &ctx->rk_a, &ctx->rk_b,
-                     &ctx->blk_edge, &ctx->runs_scratch, &ctx->row_tab, &ctx->span_key, &ctx->span_cov,
-                     &ctx->image, &ctx->xsend, &ctx->xrecv, &ctx->xscratch,
-                     &ctx->ras_masks, &ctx->xmask, &ctx->huge_offs, &ctx->huge_key, &ctx->huge_tmp, &ctx->huge_flag,
-                     &ctx->grp_tab, &ctx->grp_list, &ctx->run_lt, &ctx->rec_sp, &ctx->run_lt_sp, &ctx->row_sp, &ctx->pack_list, &ctx->pack_pix, &ctx->cache_written, &ctx->order_buf};
-    for (DevBuf* b : all) b->release();
+    for (const auto& bufs : {ctx->scene_bufs(), ctx->frame_bufs(), ctx->trimmed_bufs(), ctx->kept_bufs()})
+        for (DevBuf* b : bufs) b->release();
     for (int s = 0; s < ST_COUNT; s++) { (void)hipEventDestroy(ctx->ev0[s]); (void)hipEventDestroy(ctx->ev1[s]); }
     if (g_ktimer == &ctx->kt) g_ktimer = nullptr;           // (a timed frame of this context that failed between stage_begin and stage_end)
     for (int i = 0; i < ctx->kt.made; i++) { (void)hipEventDestroy(ctx->kt.e0[i]); (void)hipEventDestroy(ctx->kt.e1[i]); }
@@ -1191,7 +1213,6 @@ void forma_hip_destroy(forma_hip_ctx* ctx) {
     if (ctx->h_written) (void)hipHostFree(ctx->h_written);
     if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
     for (auto& c : ctx->caches) { c.tiles.release(); c.image.release(); }
-    ctx->cache_written.release();
     for (auto& r : ctx->registered) (void)hipHostUnregister(r.first);
     if (ctx->copy_stream) {
         (void)hipStreamSynchronize(ctx->copy_stream);
@@ -1503,12 +1524,7 @@ int poison_frame_buffers(forma_hip_ctx* c) {
     if (c->dbg.poison_frame < 0) return FORMA_OK;
     forma_hip_ctx* ctx = c;
     const int byte = c->dbg.poison_frame;
-    DevBuf* frame[] = {&c->scan_tmp, &c->cl_idx, &c->cl_start, &c->block_first, &c->prep_scratch, &c->seg_u, &c->seg_a, &c->seg_b,
-                       &c->sort_counters, &c->records, &c->rk_u, &c->rk_a, &c->rk_b, &c->blk_edge, &c->runs_scratch, &c->row_tab,
-                       &c->span_key, &c->span_cov, &c->ras_masks, &c->huge_offs, &c->huge_key, &c->huge_tmp, &c->huge_flag,
-                       &c->grp_tab, &c->grp_list, &c->run_lt, &c->rec_sp, &c->run_lt_sp, &c->row_sp, &c->pack_list, &c->pack_pix,
-                       &c->slice_buf};
-    for (DevBuf* b : frame) if (b->p && !b->borrowed) HIPCHECK(hipMemsetAsync(b->p, byte, b->cap, c->stream));
+    for (DevBuf* b : c->frame_bufs()) if (b->p && !b->borrowed) HIPCHECK(hipMemsetAsync(b->p, byte, b->cap, c->stream));
     return FORMA_OK;
 }
 
@@ -1674,9 +1690,8 @@ namespace {
 void share_scene(forma_hip_ctx* o) {
     for (forma_hip_ctx* sl : o->slots) {
         if (sl == o) continue;
-        sl->x.borrow(o->x); sl->y.borrow(o->y); sl->line_slot.borrow(o->line_slot); sl->geoms.borrow(o->geoms);
-        sl->style_off.borrow(o->style_off); sl->style_words.borrow(o->style_words); sl->unchanged.borrow(o->unchanged);
-        sl->images.borrow(o->images); sl->texels.borrow(o->texels); sl->layer_sf.borrow(o->layer_sf); sl->layer_col.borrow(o->layer_col);
+        const std::vector<DevBuf*> mine = sl->scene_bufs(), theirs = o->scene_bufs();
+        for (size_t i = 0; i < mine.size(); i++) mine[i]->borrow(*theirs[i]);
         sl->n_points = o->n_points; sl->n_geoms = o->n_geoms; sl->n_orders = o->n_orders; sl->n_words = o->n_words; sl->n_images = o->n_images;
         sl->max_geom_order = o->max_geom_order; sl->max_image_index = o->max_image_index; sl->any_texture = o->any_texture;
         sl->scene_has_clips = o->scene_has_clips; sl->scene_simple = o->scene_simple; sl->costly_layers = o->costly_layers; sl->have_unchanged = o->have_unchanged;
@@ -1925,20 +1940,14 @@ int forma_hip_trim(forma_hip_ctx* ctx) {
     for (forma_hip_ctx* c : all) {
         HIPCHECK(hipSetDevice(c->device));
         HIPCHECK(hipStreamSynchronize(c->stream));
-        DevBuf* frame[] = {&c->l_order, &c->l_x0, &c->l_y0, &c->l_dx, &c->l_dy, &c->l_a, &c->l_b, &c->l_c, &c->l_d, &c->l_len,
-                           &c->scan_tmp, &c->cl_idx, &c->cl_start, &c->block_first, &c->prep_scratch, &c->seg_u, &c->seg_a, &c->seg_b,
-                           &c->sort_counters, &c->records, &c->rk_u, &c->rk_a, &c->rk_b, &c->blk_edge, &c->runs_scratch, &c->row_tab,
-                           &c->span_key, &c->span_cov, &c->image, &c->xscratch, &c->ras_masks, &c->xmask,
-                           &c->huge_offs, &c->huge_key, &c->huge_tmp, &c->huge_flag, &c->grp_tab, &c->grp_list, &c->run_lt, &c->rec_sp, &c->run_lt_sp, &c->row_sp, &c->pack_list, &c->pack_pix,
-                           &c->order_buf, &c->slice_buf};
         c->order_cur = -1; c->order_pending = -1; c->order_cnt_dev = nullptr; c->order_keep_dev = nullptr;
         size_t freed = 0;
-        for (DevBuf* b : frame) { if (!b->borrowed) freed += b->cap; b->release(); }
+        for (const auto& bufs : {c->frame_bufs(), c->trimmed_bufs()})
+            for (DevBuf* b : bufs) { if (!b->borrowed) freed += b->cap; b->release(); }
         if (ctx->dbg.trim_debug) {
             size_t kept = 0;
-            DevBuf* rest[] = {&c->x, &c->y, &c->line_slot, &c->geoms, &c->style_off, &c->style_words, &c->layer_sf, &c->layer_col, &c->unchanged,
-                              &c->images, &c->texels, &c->info, &c->info_init, &c->cache_written, &c->xsend, &c->xrecv};
-            for (DevBuf* b : rest) if (!b->borrowed) kept += b->cap;
+            for (const auto& bufs : {c->scene_bufs(), c->kept_bufs()})
+                for (DevBuf* b : bufs) if (!b->borrowed) kept += b->cap;
             for (auto& tcache : c->caches) kept += tcache.tiles.cap + tcache.image.cap;
             fprintf(stderr, "[forma_hip_trim] context %p: released %zu bytes, keeps %zu\n", (void*)c, freed, kept);
         }

@@ -317,7 +317,6 @@ struct BlkEdge {             // what a k_runs tile contributes to a run that sta
 };
 size_t runs_scratch_words(size_t n);
 size_t runs_blocks(size_t n);
-// run detection + per-run cover sums; row_tab = [row_count | row_span_lo | row_span_cnt], (tiles_h + 1) words each
 // What the run kernel attaches to a record beyond the geometry — it runs on the whole chip, k_carry_rows on one CU per tile
 // row, where every scattered access per run is a cycle of that CU's address unit: the layer's style bits (SF_*, bits 21.. of
 // the record's layer word) and "unchanged" flag (bit 31 of its tile word), and a 32-bit digest per run, in stream order,
@@ -343,11 +342,12 @@ struct BlkRuns {
     uint32_t*         run_lt_out;   // (unused: the dense digests)
     uint32_t          round_tiles;  // tiles of the run kernel a round of k_carry_rows' table takes: 256 (tests: a power of two below)
 };
-// tables_are_zero: the frame's tile tables (row_tab_zero_words() words of row_tab) were cleared by an earlier kernel of this
-// frame; else k_runs_count clears them
+// run detection + per-run cover sums into the frame's tile tables.  tables_are_zero: their zeroed prefix (FrameTables::zero_words)
+// was cleared by an earlier kernel of this frame; else launch_runs clears it
+struct FrameTables;
 void launch_runs(hipStream_t s, const uint64_t* sorted, DevCount n, uint32_t tiles_w, uint32_t tiles_h, TileRecord* records,
-                 uint32_t rec_cap, uint64_t* run_keys, uint32_t* tile_first_run, BlkEdge* blk_edge,
-                 uint32_t* row_tab, uint32_t* scratch, FrameInfo* info, bool verify_plan, uint64_t spec_live44,
+                 uint32_t rec_cap, uint64_t* run_keys, BlkEdge* blk_edge, const FrameTables& tab,
+                 uint32_t* scratch, FrameInfo* info, bool verify_plan, uint64_t spec_live44,
                  bool spec_layer_sorted, PendingMasks pm, RunStyle rs, bool tables_are_zero,
                  const uint32_t* range_records /* nullable: sort_range_words() of the sort that produced `sorted` ... */,
                  uint32_t n_range_records /* ... and sort_hist_blocks() of its key count */,
@@ -411,10 +411,31 @@ static inline uint32_t paint_band_tiles(uint32_t rows, uint32_t tiles_w) {
 #define PAINT_ORDER_SUBS  64u          // heavy lists per XCD band of the painters' order (PaintParams::order_*): appends spread over
 #define PAINT_ORDER_WORDS (8u * PAINT_ORDER_SUBS)   // 512 counters — one address takes ~150 ns per returning atomic, one after the other
 #define CR_MAX_SLICES_HOST 8u         // workgroups that may share one tile row
-// the frame's tile tables, one buffer: [row_count: tiles_h + 1][row_span_lo: 8 tiles_h + 1][row_span_cnt: 8 tiles_h + 1]
-// [painter overflow counters: 2][first-run table: T][painter order counts: PAINT_ORDER_WORDS] — zeroed every frame by launch_runs —
-// then [overflow list: T][{tile, entries}: 2 T]
-// ... then [where each row's runs begin (launch_runs' chain numbering): tiles_h + 1]
+// The frame's tile tables, one buffer (forma_hip_ctx::row_tab), T = tiles_w * tiles_h: [row_count: runs per tile row, tiles_h + 1]
+// [row_span_lo | row_span_cnt: the span list of each (row, slice of the carry pre-pass), CR_MAX_SLICES_HOST * tiles_h + 1 each]
+// [the painters' overflow counts, a word each: wave -> mid tier, deep tier -> launch_paint_huge, mid tier -> deep tier]
+// [tile_first_run: T, 0 = the tile has no run][order_cnt: the painters' heavy-list counts (PaintParams::order_cnt_out), PAINT_ORDER_WORDS]
+// — that prefix (zero_words) starts every frame at zero: the frame's first kernel (ZeroJobs) or launch_runs clears it — then
+// [overflow_list: tiles the wave painters passed on, T][over2_list: {tile, entries} of the tiles beyond the deep tier, 2 T]
+// [row_base: where each row's runs begin (launch_runs' chain / BLOCKS numbering), tiles_h + 1][mid_list: ... beyond the mid tier, 2 T].
+// frame_tables(nullptr, ...): the lengths only
+struct FrameTables {
+    uint32_t *row_count, *row_span_lo, *row_span_cnt, *overflow_n, *over2_n, *mid_n, *tile_first_run, *order_cnt;
+    uint32_t *overflow_list, *over2_list, *row_base, *mid_list;
+    size_t zero_words, total_words;
+};
+static inline FrameTables frame_tables(uint32_t* base, uint32_t tiles_w, uint32_t tiles_h) {
+    const size_t T = (size_t)tiles_w * tiles_h, spans = (size_t)CR_MAX_SLICES_HOST * tiles_h + 1;
+    size_t at = 0;
+    auto take = [&](size_t words) { uint32_t* p = base ? base + at : nullptr; at += words; return p; };
+    FrameTables t;
+    t.row_count = take(tiles_h + 1); t.row_span_lo = take(spans); t.row_span_cnt = take(spans);
+    t.overflow_n = take(1); t.over2_n = take(1); t.mid_n = take(1); t.tile_first_run = take(T); t.order_cnt = take(PAINT_ORDER_WORDS);
+    t.zero_words = at;
+    t.overflow_list = take(T); t.over2_list = take(2 * T); t.row_base = take(tiles_h + 1); t.mid_list = take(2 * T);
+    t.total_words = at;
+    return t;
+}
 #ifndef RUNS_BLK_DEFAULT
 #define RUNS_BLK_DEFAULT 1              // read-back-free frames with one carry workgroup per tile row number their runs per 2 048-segment tile (BlkRuns; debug.h: runs_blk)
 #endif
@@ -428,9 +449,6 @@ static inline uint32_t paint_band_tiles(uint32_t rows, uint32_t tiles_w) {
 // frame slot at this limit (3.1 M segments), kept — like every per-frame buffer — until forma_hip_trim; a context that
 // alternates between chained and counted frames keeps the larger set.
 #endif
-static inline size_t row_tab_total_words(uint32_t tiles_w, uint32_t tiles_h);
-static inline uint32_t row_tab_zero_words(uint32_t tiles_w, uint32_t tiles_h) { return (tiles_h + 1) + 2 * (CR_MAX_SLICES_HOST * tiles_h + 1) + 3 + tiles_w * tiles_h + PAINT_ORDER_WORDS; }
-static inline size_t row_tab_total_words(uint32_t tiles_w, uint32_t tiles_h) { return (size_t)row_tab_zero_words(tiles_w, tiles_h) + 5 * (size_t)tiles_w * tiles_h + tiles_h + 1; }
 // n_slices workgroups per tile row (each a range of layers, 256 bins of layer >> bin_shift); small: the CR_CAP_S variant
 void launch_carry_rows(hipStream_t s, bool local_sort, bool small, bool half /* with small: 512-lane workgroups, slices of <= 2048 runs */,
                        uint32_t n_slices, uint32_t bin_shift,
@@ -451,29 +469,21 @@ void launch_carry_rows(hipStream_t s, bool local_sort, bool small, bool half /* 
                        bool covl = false /* one slice per row, rows of <= carry_rows_covl_cap() runs, neither small nor half: the variant that
                                             brings the row's cover sums and style summaries into LDS before the walk */,
                        BlkRuns bk = BlkRuns{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 256u} /* a COVL variant: local_sort, ONE slice per row */);
-void launch_paint(hipStream_t s, const PaintParams& p, const uint64_t* sorted, const TileRecord* records, DevCount n_runs,
-                  const uint32_t* tile_first_run, const uint32_t* row_span_lo, const uint32_t* row_span_cnt,
-                  const uint64_t* span_key, const uint4* span_cov,
-                  const uint4* layer_col /* per order: style words 2..5 (clip: word 1) */,
-                  const uint32_t* style_offsets, const uint32_t* style_words, const forma_image_t* images,
-                  const uint16_t* texels, uint8_t* image, TileCacheArgs cache, FrameInfo* info, uint32_t* overflow_n /* zeroed by launch_runs */,
-                  uint32_t* overflow_list /* tiles_w * tiles_h words */, uint32_t* over2_n /* zeroed by launch_runs */,
-                  uint32_t* over2_list /* {tile, entries} pairs: 2 * tiles_w * tiles_h words */,
-                  bool launch_deep /* false: k_paint_deep is not launched; a tile that needs it voids the frame (plan_bad) */,
+// What the painters read and write besides PaintParams: their kernels' parameters after it (paint.hip PAINT_PARAMS).
+// layer_col: per order, style words 2..5 (clip: word 1)
+struct PaintInputs {
+    const uint64_t* sorted; const TileRecord* records; DevCount n_runs; const uint32_t *tile_first_run, *row_span_lo, *row_span_cnt;
+    const uint64_t* span_key; const uint4* span_cov; const uint4* layer_col; const uint32_t *style_offsets, *style_words;
+    const forma_image_t* images; const uint16_t* texels; uint8_t* image; TileCacheArgs cache; FrameInfo* info;
+};
+// The painters; a tile beyond one tier's lists goes to the next through the overflow lists of `tab`
+void launch_paint(hipStream_t s, const PaintParams& p, const PaintInputs& in, const FrameTables& tab,
                   SpanGroups groups /* tab == nullptr: the painters scan the row lists (p.n_groups is ignored) */,
-                  bool strips = false /* four wavefronts per tile, each a 16 x 4 strip (k_paint_wave<.., NPX = 1>): frames that do not
-                                         fill the chip with one wavefront per tile; ignored with a buffer-layer cache */,
-                  bool quads = false /* four tiles per wavefront (k_paint_quad): all-solid scenes with shallow tiles; ignored otherwise */,
-                  uint32_t* mid_n = nullptr /* zeroed by launch_runs */, uint32_t* mid_list = nullptr /* {tile, entries} pairs of the tiles beyond
-                                         k_paint_deep's 1024-entry tier: 2 * tiles_w * tiles_h words (both required with launch_deep) */,
-                  uint32_t n_cus = 256,
-                  uint32_t fmt = FORMA_FORMAT_SRGB8 /* FORMA_FORMAT_*: what the painters store (image pitch: p.stride_px pixels of it) */);
+                  bool launch_deep /* false: k_paint_deep is not launched; a tile that needs it voids the frame (plan_bad) */,
+                  bool strips /* four wavefronts per tile, each a 16 x 4 strip (k_paint_wave<.., NPX = 1>); ignored with a buffer-layer cache */,
+                  bool quads /* four tiles per wavefront (k_paint_quad): all-solid scenes with shallow tiles; ignored otherwise */,
+                  uint32_t n_cus, uint32_t fmt /* FORMA_FORMAT_*: what the painters store (image pitch: p.stride_px pixels of it) */);
 // tiles whose layer list exceeds the painter's LDS lists (info->error bit 3 after launch_paint): lists in global memory,
-// offs[i] = first entry slot of tile over2_list[2 i]; g_key holds 4 entries per slot, g_tmp / g_flag one
-void launch_paint_huge(hipStream_t s, const PaintParams& p, const uint64_t* sorted, const TileRecord* records, DevCount n_runs,
-                       const uint32_t* tile_first_run, const uint32_t* row_span_lo, const uint32_t* row_span_cnt,
-                       const uint64_t* span_key, const uint4* span_cov, const uint4* layer_col,
-                       const uint32_t* style_offsets, const uint32_t* style_words, const forma_image_t* images,
-                       const uint16_t* texels, uint8_t* image, TileCacheArgs cache, FrameInfo* info, const uint32_t* over2_list,
-                       uint32_t n_tiles, const uint64_t* offs, uint64_t* g_key, uint64_t* g_tmp, uint32_t* g_flag,
-                       uint32_t fmt = FORMA_FORMAT_SRGB8);
+// offs[i] = first entry slot of tile tab.over2_list[2 i]; g_key holds 4 entries per slot, g_tmp / g_flag one
+void launch_paint_huge(hipStream_t s, const PaintParams& p, const PaintInputs& in, const FrameTables& tab, uint32_t n_tiles,
+                       const uint64_t* offs, uint64_t* g_key, uint64_t* g_tmp, uint32_t* g_flag, uint32_t fmt);

@@ -167,12 +167,8 @@ struct forma_hip_ctx {
     uint32_t n_chain_rows = 0;              //   frame tail, which sums them into the host's n_runs
     uint32_t* h_rows = nullptr;             // pinned: runs per tile row (synchronous frames), 2049 words
     uint32_t pred_max_row = 0xFFFFFFFFu;    // most runs in one tile row of the last verified frame (unknown: no local sort)
-    // tiles deeper than the painter's LDS lists (finish_paint): the launch arguments of the frame's painter and the scratch lists
-    struct HugeArgs {
-        PaintParams P; DevCount jc; TileCacheArgs tc;
-        const uint32_t* tile_first_run; const uint32_t* row_span_lo; const uint32_t* row_span_cnt;
-        uint32_t* over2_n; uint32_t* over2_list; uint32_t T; uint32_t fmt;
-    } huge{};
+    // tiles deeper than the painter's LDS lists (finish_paint): what of the painter launch the context does not hold; the scratch lists
+    struct HugeArgs { PaintParams P; DevCount jc; TileCacheArgs tc; uint32_t fmt; } huge{};
     DevBuf huge_offs, huge_key, huge_tmp, huge_flag;
     // band
     uint32_t band_row0 = 0, band_row1 = 0;
@@ -222,6 +218,17 @@ struct forma_hip_ctx {
     // what the last frame wrote, for forma_hip_tiles_written (host-side Flusher / generic Layout::write)
     uint32_t lw_tiles_w = 0, lw_tiles_h = 0, lw_tx0 = 0, lw_tx1 = 0, lw_ty0 = 0, lw_ty1 = 0;
     bool lw_valid = false, lw_cache = false, lw_flags_on_host = false;
+
+    // The device buffers by lifetime (the caches' aside); forma_hip_destroy releases all four.  The scene: frame slots borrow it
+    std::vector<DevBuf*> scene_bufs() { return {&x, &y, &line_slot, &geoms, &style_off, &style_words, &unchanged, &images, &texels, &layer_sf, &layer_col}; }
+    // per-frame scratch that a frame writes before it reads: poison_frame_buffers refills it, forma_hip_trim releases it
+    std::vector<DevBuf*> frame_bufs() { return {&scan_tmp, &cl_idx, &cl_start, &block_first, &prep_scratch, &seg_u, &seg_a, &seg_b, &sort_counters,
+        &records, &rk_u, &rk_a, &rk_b, &blk_edge, &runs_scratch, &row_tab, &span_key, &span_cov, &ras_masks, &huge_offs, &huge_key, &huge_tmp,
+        &huge_flag, &grp_tab, &grp_list, &run_lt, &rec_sp, &run_lt_sp, &row_sp, &pack_list, &pack_pix, &slice_buf}; }
+    // released by trim, not refilled: parity line parameters, the scratch image (a cropped frame leaves the rest alone), exchange scratch, order lists
+    std::vector<DevBuf*> trimmed_bufs() { return {&l_order, &l_x0, &l_y0, &l_dx, &l_dy, &l_a, &l_b, &l_c, &l_d, &l_len, &image, &xscratch, &xmask, &order_buf}; }
+    // kept by trim, like the scene: FrameInfo and its template, cache frames' written-tile flags, the exchange's buckets
+    std::vector<DevBuf*> kept_bufs() { return {&info, &info_init, &cache_written, &xsend, &xrecv}; }
 };
 
 

@@ -645,19 +645,16 @@ size_t runs_chain_words(size_t n) { return (n + RN_TILE - 1) / RN_TILE + 1; }   
 size_t runs_blocks(size_t n) { return (n + RW_CHUNK - 1) / RW_CHUNK + 4; }      // BlkEdge entries: one per wave chunk
 
 void launch_runs(hipStream_t s, const uint64_t* sorted, DevCount nc, uint32_t tiles_w, uint32_t tiles_h, TileRecord* records,
-                 uint32_t rec_cap, uint64_t* run_keys, uint32_t* tile_first_run, BlkEdge* blk_edge, uint32_t* row_tab,
+                 uint32_t rec_cap, uint64_t* run_keys, BlkEdge* blk_edge, const FrameTables& tab,
                  uint32_t* scratch, FrameInfo* info, bool verify_plan, uint64_t spec_live44, bool spec_layer_sorted,
                  PendingMasks pm, RunStyle rs, bool tables_are_zero, const uint32_t* range_records, uint32_t n_range_records, int what,
                  uint32_t* chain_row_base, bool chain_status_is_zero, bool blocks) {
-    // per-frame tile tables: [row_count | row_span_lo | row_span_cnt | painter overflow counters (2) | first-run table] are
-    // contiguous (api.cpp lays them out so) and start from zero — cleared by k_runs_count, unless an earlier kernel of the frame
-    // already did (api.cpp folds that into the frame's first kernel); 0 in the first-run table = the tile has no run
-    const uint32_t zero_words = tables_are_zero ? 0u : row_tab_zero_words(tiles_w, tiles_h);
+    // the zeroed prefix of the tile tables: k_runs_count clears it where it runs, a memset here otherwise — unless an earlier kernel
+    // of the frame did; 0 in the first-run table = the tile has no run
+    const uint32_t zero_words = tables_are_zero ? 0u : (uint32_t)tab.zero_words;
+    if (zero_words && (nc.bound ? chain_row_base != nullptr : (what & 1) != 0)) (void)hipMemsetAsync(tab.row_count, 0, (size_t)zero_words * 4, s);
     if (nc.bound == 0) {
-        if (what & 1) {
-            if (zero_words) (void)hipMemsetAsync(row_tab, 0, (size_t)zero_words * 4, s);
-            (void)hipMemsetAsync(&info->n_runs, 0, 4, s);
-        }
+        if (what & 1) (void)hipMemsetAsync(&info->n_runs, 0, 4, s);
         return;
     }
     const uint32_t ntiles = (nc.bound + RN_TILE - 1) / RN_TILE;
@@ -665,33 +662,27 @@ void launch_runs(hipStream_t s, const uint64_t* sorted, DevCount nc, uint32_t ti
     const uint32_t cgrid = std::min<uint32_t>((ntiles + 1) / 2, 4096u);
     uint32_t* chunk_counts = scratch + ntiles + 8;                      // 4 per tile (+ slack for the last wave's second half)
     const int scanned = ntiles > 16384 ? 1 : 0;
-    if (chain_row_base && blocks) {
-        // no counting pass and no look-back (k_runs_wave<2>): runs numbered per 2 048-segment tile, `records` / rs.run_lt are the SPARSE
-        // arrays (n.bound entries), the head of `scratch` takes the tiles' head counts (every tile of the stream writes its own)
-        if (zero_words) (void)hipMemsetAsync(row_tab, 0, (size_t)zero_words * 4, s);
-        FORMA_LAUNCH(k_runs_wave<2>, dim3(ntiles + 1), dim3(RW_THREADS), 0, s, sorted, nc, tiles_w, tiles_h, records, rec_cap,
-                           run_keys, tile_first_run, blk_edge, row_tab, (const uint32_t*)nullptr, 0, (const uint32_t*)nullptr, info, rs,
-                           RunChain{scratch, chain_row_base, spec_live44, flags, pm, range_records, n_range_records});
-        return;
-    }
     if (chain_row_base) {
-        // no counting pass (k_runs_wave<1>): the tables and the tiles' status words (the head of `scratch`) are cleared by an
-        // earlier kernel of the frame or by two memsets here; one more workgroup (the first) keeps house
-        if (zero_words) (void)hipMemsetAsync(row_tab, 0, (size_t)zero_words * 4, s);
-        if (!chain_status_is_zero) (void)hipMemsetAsync(scratch, 0, (size_t)ntiles * 4, s);
-        FORMA_LAUNCH(k_runs_wave<1>, dim3(ntiles + 1), dim3(RW_THREADS), 0, s, sorted, nc, tiles_w, tiles_h, records, rec_cap,
-                           run_keys, tile_first_run, blk_edge, row_tab, (const uint32_t*)nullptr, 0, (const uint32_t*)nullptr, info, rs,
-                           RunChain{scratch, chain_row_base, spec_live44, flags, pm, range_records, n_range_records});
+        // no counting pass.  k_runs_wave<1>: runs numbered per tile row, the tiles' status words (the head of `scratch`) cleared by an
+        // earlier kernel of the frame or a memset here, one more workgroup (the first) keeps house.  k_runs_wave<2> (`blocks`): per
+        // 2 048-segment tile and no look-back, `records` / rs.run_lt are the SPARSE arrays (n.bound entries), the head of `scratch`
+        // takes the tiles' head counts (every tile of the stream writes its own)
+        if (!blocks && !chain_status_is_zero) (void)hipMemsetAsync(scratch, 0, (size_t)ntiles * 4, s);
+#define RW_CHAIN(M_) FORMA_LAUNCH(k_runs_wave<M_>, dim3(ntiles + 1), dim3(RW_THREADS), 0, s, sorted, nc, tiles_w, tiles_h, records, rec_cap, \
+                                  run_keys, tab.tile_first_run, blk_edge, tab.row_count, (const uint32_t*)nullptr, 0, (const uint32_t*)nullptr, \
+                                  info, rs, RunChain{scratch, chain_row_base, spec_live44, flags, pm, range_records, n_range_records})
+        if (blocks) RW_CHAIN(2); else RW_CHAIN(1);
+#undef RW_CHAIN
         return;
     }
     if (what & 1) {
-        FORMA_LAUNCH(k_runs_count, dim3(cgrid + 1), dim3(RC_THREADS), 0, s, sorted, nc, tiles_w, tiles_h, scratch, chunk_counts, row_tab,
+        FORMA_LAUNCH(k_runs_count, dim3(cgrid + 1), dim3(RC_THREADS), 0, s, sorted, nc, tiles_w, tiles_h, scratch, chunk_counts, tab.row_count,
                            zero_words, info, spec_live44, flags, pm, range_records, n_range_records);
         if (scanned) launch_scan_small_u32(s, scratch, nc, RN_TILE, &info->n_runs);   // exclusive, in place; total -> n_runs
     }
     if (what & 2)
         FORMA_LAUNCH(k_runs_wave<0>, dim3(ntiles), dim3(RW_THREADS), 0, s, sorted, nc, tiles_w, tiles_h, records, rec_cap,
-                           run_keys, tile_first_run, blk_edge, row_tab, (const uint32_t*)scratch, scanned,
+                           run_keys, tab.tile_first_run, blk_edge, tab.row_count, (const uint32_t*)scratch, scanned,
                            (const uint32_t*)chunk_counts, info, rs, RunChain{nullptr, nullptr, 0ull, 0u, PendingMasks{nullptr, 0u}, nullptr, 0u});
 }
 uint32_t runs_edge_segments() { return RW_CHUNK; }
@@ -3308,8 +3299,6 @@ __global__ __launch_bounds__(64, PAINT_SIMPLE_OCC) void k_paint_quad(PaintParams
     }
 }
 
-#define PAINT_ARGS P, tile, sorted, records, n_runs, tile_first_run, row_span_lo, row_span_cnt, span_key, span_cov, layer_col, \
-                   style_offsets, style_words, images, texels, image, cache, info
 #define PAINT_PARAMS PaintParams P, const uint64_t* __restrict__ sorted, const TileRecord* __restrict__ records, DevCount nc_runs, \
                      const uint32_t* __restrict__ tile_first_run, const uint32_t* __restrict__ row_span_lo, \
                      const uint32_t* __restrict__ row_span_cnt, const uint64_t* __restrict__ span_key, \
@@ -3317,11 +3306,15 @@ __global__ __launch_bounds__(64, PAINT_SIMPLE_OCC) void k_paint_quad(PaintParams
                      const uint32_t* __restrict__ style_offsets, const uint32_t* __restrict__ style_words, \
                      const forma_image_t* __restrict__ images, const uint16_t* __restrict__ texels, uint8_t* __restrict__ image, \
                      TileCacheArgs cache, FrameInfo* __restrict__ info
+// ... as paint_tile's arguments
+#define PAINT_TILE_ARGS P, tile, sorted, records, n_runs, tile_first_run, row_span_lo, row_span_cnt, span_key, span_cov, layer_col, \
+                        style_offsets, style_words, images, texels, image, cache, info
+// ... and as the launchers pass them (PaintInputs, common.h)
+#define PAINT_INPUTS(I) (I).sorted, (I).records, (I).n_runs, (I).tile_first_run, (I).row_span_lo, (I).row_span_cnt, (I).span_key, \
+                        (I).span_cov, (I).layer_col, (I).style_offsets, (I).style_words, (I).images, (I).texels, (I).image, (I).cache, (I).info
 
 #define PAINT_MAXE_DEEP 4096
 #define PAINT_MAXE_MID  1024
-#define PAINT_ARGS2 P, tile, sorted, records, n_runs, tile_first_run, row_span_lo, row_span_cnt, span_key, span_cov, layer_col, \
-                    style_offsets, style_words, images, texels, image, cache, info
 // The deep tiles the first launch could not hold, in two tiers.  MAXE = 1024 (20 KB of lists + 7 KB of paint_tile's own LDS,
 // 105 VGPRs: FOUR workgroups per CU) takes the wave painters' overflow list; what does not fit it goes on to MAXE = 4096 (80 KB of
 // lists: one workgroup per CU), and from there to k_paint_huge.  Until round 5 there was only the 4096-entry kernel: one
@@ -3340,7 +3333,7 @@ __global__ __launch_bounds__(256) void k_paint_deep(PAINT_PARAMS, const uint32_t
     const uint32_t n_runs = dev_count(nc_runs);
     for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
         const uint32_t tile = list[(size_t)STRIDE * i];
-        paint_tile<FMT>(MAXE, MAXE / 4, e_key, e_tmp, e_flag, PAINT_ARGS2, over_n, over_list);
+        paint_tile<FMT>(MAXE, MAXE / 4, e_key, e_tmp, e_flag, PAINT_TILE_ARGS, over_n, over_list);
         __syncthreads();
     }
 }
@@ -3355,19 +3348,14 @@ __global__ __launch_bounds__(256) void k_paint_huge(PAINT_PARAMS, const uint32_t
     for (uint32_t i = blockIdx.x; i < n_tiles; i += gridDim.x) {
         const uint32_t tile = over2_list[2 * i], cap = over2_list[2 * i + 1];
         const uint64_t o = offs[i];
-        paint_tile<FMT>(cap, cap, g_key + 4 * o, g_tmp + o, g_flag + o, PAINT_ARGS2, nullptr, nullptr);
+        paint_tile<FMT>(cap, cap, g_key + 4 * o, g_tmp + o, g_flag + o, PAINT_TILE_ARGS, nullptr, nullptr);
         __syncthreads();
     }
 }
 
 template <int FMT>
-static void launch_paint_fmt(hipStream_t s, const PaintParams& p, const uint64_t* sorted, const TileRecord* records, DevCount n_runs,
-                             const uint32_t* tile_first_run, const uint32_t* row_span_lo, const uint32_t* row_span_cnt,
-                             const uint64_t* span_key, const uint4* span_cov, const uint4* layer_col,
-                             const uint32_t* style_offsets, const uint32_t* style_words, const forma_image_t* images,
-                             const uint16_t* texels, uint8_t* image, TileCacheArgs cache, FrameInfo* info, uint32_t* overflow_n,
-                             uint32_t* overflow_list, uint32_t* over2_n, uint32_t* over2_list, bool launch_deep, SpanGroups groups, bool strips, bool quads,
-                             uint32_t* mid_n, uint32_t* mid_list, uint32_t n_cus) {
+static void launch_paint_fmt(hipStream_t s, const PaintParams& p, const PaintInputs& in, const FrameTables& tab, SpanGroups groups,
+                             bool launch_deep, bool strips, bool quads, uint32_t n_cus) {
     const uint32_t T = p.tiles_w * p.tiles_h;
     if (T == 0 || p.crop_y1 <= p.crop_y0) return;
     const uint32_t per = paint_band_tiles(p.crop_y1 - p.crop_y0, p.tiles_w);
@@ -3377,19 +3365,19 @@ static void launch_paint_fmt(hipStream_t s, const PaintParams& p, const uint64_t
     const bool simple = (p.scene_simple && !no_simple) || force_simple, one = p.n_slices == 1u;
     // strips (four wavefronts per tile, NPX = 1): never with a buffer-layer cache — a tile's cache entry is read by every strip
     // and rewritten by the first one that finishes
-    if (cache.tiles) strips = false;
+    if (in.cache.tiles) strips = false;
     // quads (k_paint_quad: four tiles per wavefront): all-solid scenes with shallow tiles, no cache
-    if (quads && simple && !cache.tiles) {
+    if (quads && simple && !in.cache.tiles) {
         const uint32_t qper = QUAD_ROW_XCD ? ((p.crop_y1 - p.crop_y0 + 7u) / 8u) * ((p.tiles_w + 3u) / 4u)
                                             : ((p.crop_y1 - p.crop_y0) * ((p.tiles_w + 3u) / 4u) + 7u) / 8u;
-        if (one) FORMA_LAUNCH((k_paint_quad<true, FMT>), dim3(qper * 8), dim3(64), 0, s, p, sorted, records, n_runs, tile_first_run, row_span_lo, row_span_cnt,
-                              span_key, span_cov, layer_col, image, info, overflow_n, overflow_list, launch_deep ? 1u : 0u, groups);
-        else FORMA_LAUNCH((k_paint_quad<false, FMT>), dim3(qper * 8), dim3(64), 0, s, p, sorted, records, n_runs, tile_first_run, row_span_lo, row_span_cnt,
-                          span_key, span_cov, layer_col, image, info, overflow_n, overflow_list, launch_deep ? 1u : 0u, groups);
+#define PQ_LAUNCH(O_) FORMA_LAUNCH((k_paint_quad<O_, FMT>), dim3(qper * 8), dim3(64), 0, s, p, in.sorted, in.records, in.n_runs, \
+                                   in.tile_first_run, in.row_span_lo, in.row_span_cnt, in.span_key, in.span_cov, in.layer_col, in.image, \
+                                   in.info, tab.overflow_n, tab.overflow_list, launch_deep ? 1u : 0u, groups)
+        if (one) PQ_LAUNCH(true); else PQ_LAUNCH(false);
+#undef PQ_LAUNCH
     } else {
-#define PW_LAUNCH(S_, O_, N_) FORMA_LAUNCH((k_paint_wave<S_, O_, N_, FMT>), dim3(N_ == 1 ? per * 32 : (per + (p.order_cnt_out ? p.order_hcap : 0u)) * 8), dim3(64), 0, s, p, sorted, records, n_runs, \
-                                             tile_first_run, row_span_lo, row_span_cnt, span_key, span_cov, layer_col, style_offsets, style_words, \
-                                             images, texels, image, cache, info, overflow_n, overflow_list, launch_deep ? 1u : 0u, groups)
+#define PW_LAUNCH(S_, O_, N_) FORMA_LAUNCH((k_paint_wave<S_, O_, N_, FMT>), dim3(N_ == 1 ? per * 32 : (per + (p.order_cnt_out ? p.order_hcap : 0u)) * 8), dim3(64), 0, s, p, \
+                                             PAINT_INPUTS(in), tab.overflow_n, tab.overflow_list, launch_deep ? 1u : 0u, groups)
 #define PW_LAUNCH_N(S_, O_) do { if (strips) PW_LAUNCH(S_, O_, 1); else PW_LAUNCH(S_, O_, 4); } while (0)
     if (simple) { if (one) PW_LAUNCH_N(true, true); else PW_LAUNCH_N(true, false); }
     else { if (one) PW_LAUNCH_N(false, true); else PW_LAUNCH_N(false, false); }
@@ -3400,43 +3388,25 @@ static void launch_paint_fmt(hipStream_t s, const PaintParams& p, const uint64_t
     // mid tier: four workgroups per CU; its own overflow ({tile, entries} pairs in mid_list) goes to the 4096-entry tier, whose
     // launch is empty (~4 us) in every frame without a tile beyond 1024 entries — paid only by frames that have deep tiles at all
     const uint32_t g_mid = std::min<uint32_t>(T, 4u * n_cus), g_deep = std::min<uint32_t>(T, n_cus);
-    FORMA_LAUNCH((k_paint_deep<PAINT_MAXE_MID, 1, FMT>), dim3(g_mid), dim3(256), 0, s, p, sorted, records, n_runs, tile_first_run,
-                       row_span_lo, row_span_cnt, span_key, span_cov, layer_col, style_offsets, style_words, images,
-                       texels, image, cache, info, (const uint32_t*)overflow_n, (const uint32_t*)overflow_list, mid_n, mid_list);
-    FORMA_LAUNCH((k_paint_deep<PAINT_MAXE_DEEP, 2, FMT>), dim3(g_deep), dim3(256), 0, s, p, sorted, records, n_runs, tile_first_run,
-                       row_span_lo, row_span_cnt, span_key, span_cov, layer_col, style_offsets, style_words, images,
-                       texels, image, cache, info, (const uint32_t*)mid_n, (const uint32_t*)mid_list, over2_n, over2_list);
+    FORMA_LAUNCH((k_paint_deep<PAINT_MAXE_MID, 1, FMT>), dim3(g_mid), dim3(256), 0, s, p, PAINT_INPUTS(in),
+                 (const uint32_t*)tab.overflow_n, (const uint32_t*)tab.overflow_list, tab.mid_n, tab.mid_list);
+    FORMA_LAUNCH((k_paint_deep<PAINT_MAXE_DEEP, 2, FMT>), dim3(g_deep), dim3(256), 0, s, p, PAINT_INPUTS(in),
+                 (const uint32_t*)tab.mid_n, (const uint32_t*)tab.mid_list, tab.over2_n, tab.over2_list);
 }
-void launch_paint(hipStream_t s, const PaintParams& p, const uint64_t* sorted, const TileRecord* records, DevCount n_runs,
-                  const uint32_t* tile_first_run, const uint32_t* row_span_lo, const uint32_t* row_span_cnt,
-                  const uint64_t* span_key, const uint4* span_cov, const uint4* layer_col,
-                  const uint32_t* style_offsets, const uint32_t* style_words, const forma_image_t* images,
-                  const uint16_t* texels, uint8_t* image, TileCacheArgs cache, FrameInfo* info, uint32_t* overflow_n,
-                  uint32_t* overflow_list, uint32_t* over2_n, uint32_t* over2_list, bool launch_deep, SpanGroups groups, bool strips, bool quads,
-                  uint32_t* mid_n, uint32_t* mid_list, uint32_t n_cus, uint32_t fmt) {
-#define LP_ARGS s, p, sorted, records, n_runs, tile_first_run, row_span_lo, row_span_cnt, span_key, span_cov, layer_col, style_offsets, \
-                style_words, images, texels, image, cache, info, overflow_n, overflow_list, over2_n, over2_list, launch_deep, groups, strips, \
-                quads, mid_n, mid_list, n_cus
-    if (fmt == FORMA_FORMAT_LINEAR_F16) launch_paint_fmt<FMT_F16>(LP_ARGS);
-    else launch_paint_fmt<FMT_SRGB8>(LP_ARGS);
-#undef LP_ARGS
+// FORMA_FORMAT_* -> the painters' FMT: f(std::integral_constant<int, FMT>())
+template <class F> static void with_fmt(uint32_t fmt, F&& f) {
+    if (fmt == FORMA_FORMAT_LINEAR_F16) f(std::integral_constant<int, FMT_F16>());
+    else f(std::integral_constant<int, FMT_SRGB8>());
 }
-
-void launch_paint_huge(hipStream_t s, const PaintParams& p, const uint64_t* sorted, const TileRecord* records, DevCount n_runs,
-                       const uint32_t* tile_first_run, const uint32_t* row_span_lo, const uint32_t* row_span_cnt,
-                       const uint64_t* span_key, const uint4* span_cov, const uint4* layer_col,
-                       const uint32_t* style_offsets, const uint32_t* style_words, const forma_image_t* images,
-                       const uint16_t* texels, uint8_t* image, TileCacheArgs cache, FrameInfo* info, const uint32_t* over2_list,
-                       uint32_t n_tiles, const uint64_t* offs, uint64_t* g_key, uint64_t* g_tmp, uint32_t* g_flag, uint32_t fmt) {
+void launch_paint(hipStream_t s, const PaintParams& p, const PaintInputs& in, const FrameTables& tab, SpanGroups groups,
+                  bool launch_deep, bool strips, bool quads, uint32_t n_cus, uint32_t fmt) {
+    with_fmt(fmt, [&](auto F) { launch_paint_fmt<decltype(F)::value>(s, p, in, tab, groups, launch_deep, strips, quads, n_cus); });
+}
+void launch_paint_huge(hipStream_t s, const PaintParams& p, const PaintInputs& in, const FrameTables& tab, uint32_t n_tiles,
+                       const uint64_t* offs, uint64_t* g_key, uint64_t* g_tmp, uint32_t* g_flag, uint32_t fmt) {
     if (n_tiles == 0) return;
-    if (fmt == FORMA_FORMAT_LINEAR_F16)
-        FORMA_LAUNCH((k_paint_huge<FMT_F16>), dim3(n_tiles < 256 ? n_tiles : 256), dim3(256), 0, s, p, sorted, records, n_runs, tile_first_run,
-                     row_span_lo, row_span_cnt, span_key, span_cov, layer_col, style_offsets, style_words, images, texels, image,
-                     cache, info, over2_list, n_tiles, offs, g_key, g_tmp, g_flag);
-    else
-        FORMA_LAUNCH((k_paint_huge<FMT_SRGB8>), dim3(n_tiles < 256 ? n_tiles : 256), dim3(256), 0, s, p, sorted, records, n_runs, tile_first_run,
-                     row_span_lo, row_span_cnt, span_key, span_cov, layer_col, style_offsets, style_words, images, texels, image,
-                     cache, info, over2_list, n_tiles, offs, g_key, g_tmp, g_flag);
+    with_fmt(fmt, [&](auto F) { FORMA_LAUNCH((k_paint_huge<decltype(F)::value>), dim3(n_tiles < 256 ? n_tiles : 256), dim3(256), 0, s, p,
+                                             PAINT_INPUTS(in), (const uint32_t*)tab.over2_list, n_tiles, offs, g_key, g_tmp, g_flag); });
 }
 
 // ================================================================================================

@@ -69,6 +69,23 @@ class FlattenTablesT(C.Structure):
                 ("sp2x", C.c_void_p), ("sp2y", C.c_void_p), ("n_splines", C.c_size_t)]
 
 
+class AffineRangeT(C.Structure):
+    _fields_ = [("first", C.c_uint64), ("count", C.c_uint64), ("m", C.c_float * 6)]
+
+
+class KeepRangeT(C.Structure):
+    _fields_ = [("first", C.c_uint64), ("count", C.c_uint64)]
+
+
+class CountersT(C.Structure):
+    _fields_ = [("geometry_points", C.c_uint64), ("geometry_uploads", C.c_uint64), ("geometry_appends", C.c_uint64),
+                ("geometry_retains", C.c_uint64), ("geometry_bytes_h2d", C.c_uint64), ("geometry_bytes_d2h", C.c_uint64),
+                ("frames", C.c_uint64), ("frames_learned", C.c_uint64), ("frames_rerun", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 # every symbol include/forma_hip.h declares: (name, restype, argtypes)
 _vp, _sz, _u32, _i = C.c_void_p, C.c_size_t, C.c_uint32, C.c_int
 SYMBOLS = {
@@ -82,6 +99,10 @@ SYMBOLS = {
     "forma_hip_set_styles": (_i, [_vp, _vp, _sz, _vp, _sz, _vp]),
     "forma_hip_set_images": (_i, [_vp, _vp, _sz, _vp, _sz]),
     "forma_hip_flatten": (_i, [_vp, _vp, _vp, _vp]),
+    "forma_hip_geometry_append": (_i, [_vp, _vp, _vp, _vp, _sz]),
+    "forma_hip_geometry_retain": (_i, [_vp, _vp, _sz, _vp, _sz]),
+    "forma_hip_read_geometry": (_i, [_vp, _vp, _vp, _vp, _sz, _vp]),
+    "forma_hip_counters": (_i, [_vp, _vp]),
     "forma_hip_prepare_lines": (_i, [_vp, _u32, _u32] + [_vp] * 10),
     "forma_hip_rasterize": (_i, [_vp, _sz] + [_vp] * 10 + [_vp, _sz, _vp]),
     "forma_hip_sort": (_i, [_vp, _vp, _sz, _i]),

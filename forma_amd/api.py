@@ -59,6 +59,8 @@ def _host():
         L.forma_host_batch_points.argtypes = [vp]; L.forma_host_batch_points.restype = sz
         L.forma_host_batch_flatten.argtypes = [vp, vp, vp, vp, vp]; L.forma_host_batch_flatten.restype = C.c_int
         L.forma_host_batch_tables.argtypes = [vp, vp]
+        if hasattr(L, "forma_host_batch_append"):         # (absent in an older build loaded through FORMA_HIP_LIB: tools' A/B runs)
+            L.forma_host_batch_append.argtypes = [vp, vp]; L.forma_host_batch_append.restype = C.c_int
         _host_bound = True
     return L
 
@@ -382,6 +384,7 @@ class _Shared:
         self.geom_id_to_order: Dict[int, Optional[int]] = {}
         self.next_geom_id = 1
         self.geometry_version = 0
+        self.pushes_epoch = 0          # bumped whenever `pushes` changes other than by an append at its end (compact_geom)
         self.table_version = 0         # bumped by every change that the per-frame layer / style tables depend on
         self.unchanged_version = 0     # bumped when a render call changes some layer's is_unchanged set
 
@@ -529,6 +532,7 @@ class Composition:
             live = [p for p in sh.pushes if p[0] in sh.geom_id_to_order]
             if len(live) != len(sh.pushes):
                 sh.pushes = live
+                sh.pushes_epoch += 1
                 sh.geometry_version += 1
                 return True
         return False
@@ -694,11 +698,18 @@ class BufferBuilder:
 class Renderer:
     """`forma::hip::Renderer`: same three methods as `cpu::Renderer` (cpu/renderer.rs:61-224)."""
 
-    def __init__(self, device: int = 0, devices=None, frames_in_flight: int = 1):
+    def __init__(self, device: int = 0, devices=None, frames_in_flight: int = 1, resident_geometry: bool = False):
         """`Renderer::new()` (cpu/renderer.rs:63-65).  `devices`: one renderer over several GPUs of this process
         (forma_hip_create_multi — the Rust shim's `Renderer::with_devices`); `frames_in_flight`: device-resident frames
-        are pipelined inside the renderer (forma_hip_set_frames_in_flight)."""
+        are pipelined inside the renderer (forma_hip_set_frames_in_flight); `resident_geometry`: the setting for scenes
+        whose geometry changes — the device's geometry store is appended to and compacted in place, at the cost of the
+        edit, instead of being flattened and uploaded again as a whole (`host_tables` then holds no geometry: see
+        `read_geometry`)."""
         self._ctx = Context(device, devices=devices, frames_in_flight=frames_in_flight)
+        self._resident = bool(resident_geometry)
+        self._dev_pushes: list = []                      # resident mode: the pushes on the device, in store order ...
+        self._dev_points: List[int] = []                 # ... their point counts ...
+        self._dev_epoch = None                           # ... and the _Shared.pushes_epoch they were taken at
         self._caches = set()
         self._geom_version = None
         self._geom_owner = None
@@ -738,6 +749,83 @@ class Renderer:
         self._slot_of = slot_of
         self._geom_version = sh.geometry_version
         self._geom_owner = sh
+
+    # -- resident mode: reconcile the device's store with the composition's pushes, at the cost of the difference
+    def _reconcile_geometry(self, comp: Composition):
+        sh = comp._shared
+        dev = self._dev_pushes
+        if self._geom_owner is not sh or self._dev_epoch is None:
+            return self._upload_resident(comp)
+        if self._dev_epoch != sh.pushes_epoch:
+            # pushes went away (compact_geom): the survivors must be the device's pushes in their order, new ones behind them
+            kept, j = [], 0
+            for i, p in enumerate(dev):
+                if j < len(sh.pushes) and sh.pushes[j] is p:
+                    kept.append(i); j += 1
+            known = {id(p) for p in dev}
+            if any(id(q) in known for q in sh.pushes[j:]):
+                return self._upload_resident(comp)        # (an old push behind a new one, or another order: the full path)
+            # SegmentBuffer::retain: ranges of whole pushes, merged where they touch; slots renumbered densely in order of
+            # first appearance among the survivors — what a from-scratch upload of them would number
+            starts = np.concatenate(([0], np.cumsum(self._dev_points))).astype(np.int64) if dev else np.zeros(1, np.int64)
+            ranges: List[List[int]] = []
+            slot_of: Dict[int, int] = {}
+            for i in kept:
+                first, count = int(starts[i]), self._dev_points[i]
+                slot_of.setdefault(dev[i][0], len(slot_of))
+                if ranges and ranges[-1][0] + ranges[-1][1] == first:
+                    ranges[-1][1] += count
+                else:
+                    ranges.append([first, count])
+            remap = np.full(max(len(self._slot_of), 1), NONE, np.uint32)
+            for g, old in self._slot_of.items():
+                if g in slot_of:
+                    remap[old] = slot_of[g]
+            self._ctx.geometry_retain([(f, c) for f, c in ranges], remap[: len(self._slot_of)])
+            self._dev_pushes = [dev[i] for i in kept]
+            self._dev_points = [self._dev_points[i] for i in kept]
+            self._slot_of = slot_of
+            self._dev_epoch = sh.pushes_epoch
+            dev = self._dev_pushes
+        elif len(sh.pushes) < len(dev) or (dev and sh.pushes[len(dev) - 1] is not dev[-1]):
+            return self._upload_resident(comp)
+        new = sh.pushes[len(dev):]                        # the pure append: O(new pushes)
+        if new:
+            H = _host()
+            items = []
+            for p in new:
+                items.append((p[1], self._slot_of.setdefault(p[0], len(self._slot_of))))
+            self._ctx.geometry_append_paths(items)
+            self._dev_pushes.extend(new)
+            self._dev_points.extend(int(H.forma_host_path_points(p[1]._h)) for p in new)
+        self._geom_version = sh.geometry_version
+
+    def _upload_resident(self, comp: Composition):
+        """the full path of the resident mode: an empty store, then every push appended (flattened on the device, no copy back)"""
+        sh = comp._shared
+        self._ctx.set_geometry(np.zeros(0, np.float32), np.zeros(0, np.float32), np.zeros(0, np.uint32))
+        self._slot_of = {}
+        items = [(p[1], self._slot_of.setdefault(p[0], len(self._slot_of))) for p in sh.pushes]
+        if items:
+            self._ctx.geometry_append_paths(items)
+        H = _host()
+        self._dev_pushes = list(sh.pushes)
+        self._dev_points = [int(H.forma_host_path_points(p[1]._h)) for p in sh.pushes]
+        self._dev_epoch = sh.pushes_epoch
+        self._geom_version = sh.geometry_version
+        self._geom_owner = sh
+        for k in ("x", "y", "line_slot"):
+            self.host_tables.pop(k, None)
+
+    def read_geometry(self):
+        """(x, y, line_slot) of the device's geometry store, read back (forma_hip_read_geometry) — in both modes what
+        forma_hip_set_geometry was, or would have been, given"""
+        return self._ctx.read_geometry()
+
+    def counters(self) -> Dict[str, int]:
+        """forma_hip_counters: points in the store, uploads / appends / retains and their bytes, frames rendered, learned
+        (synchronous) and re-run"""
+        return self._ctx.counters()
 
     def _upload_tables(self, comp: Composition, cache_id: Optional[int]):
         sh = comp._shared
@@ -823,7 +911,11 @@ class Renderer:
     def _upload_scene(self, composition: Composition, cache_id: Optional[int]):
         composition.compact_geom()                            # renderer.rs:113
         sh = composition._shared
-        if self._geom_owner is not sh or self._geom_version != sh.geometry_version:
+        if getattr(self, "_resident", False):
+            # (a path without points bumps no geometry version but still takes a slot, like in a from-scratch upload)
+            if self._geom_owner is not sh or self._geom_version != sh.geometry_version or len(sh.pushes) != len(self._dev_pushes):
+                self._reconcile_geometry(composition)
+        elif self._geom_owner is not sh or self._geom_version != sh.geometry_version:
             self._upload_geometry(composition)
         # the layer / style / unchanged tables stay resident: they are rebuilt only when something they depend on changed
         key = (sh, sh.table_version, sh.unchanged_version if cache_id is not None else -1, cache_id)

@@ -116,6 +116,77 @@ class Context:
         tx = np.ascontiguousarray(texels, np.uint16).reshape(-1, 4)
         self._check(self._L.forma_hip_set_images(self._h, _p(im), len(im), _p(tx), len(tx)))
 
+    # ---- the geometry store as an incremental store
+    @staticmethod
+    def _flatten_tables(t):
+        from ._lib import FlattenTablesT
+        ft = FlattenTablesT()
+        keep = []
+        for name, _ in FlattenTablesT._fields_:
+            if name.startswith("n_"):
+                setattr(ft, name, int(t[name]))
+            else:
+                a = np.ascontiguousarray(t[name]); keep.append(a)
+                setattr(ft, name, a.ctypes.data)
+        return ft, keep
+
+    def geometry_append(self, t, line_slot, affines=()):
+        """forma_hip_geometry_append on caller-supplied work items (as flatten_tables): flatten them on the device into the
+        tail of the store.  line_slot: one entry per point, the last one NONE; affines: [(first, count, m[6])], ascending."""
+        from ._lib import AffineRangeT
+        ft, keep = self._flatten_tables(t)
+        ls = np.ascontiguousarray(line_slot, np.uint32)
+        assert len(ls) == int(t["n_points"])
+        ar = (AffineRangeT * max(len(affines), 1))()
+        for i, (first, count, m) in enumerate(affines):
+            ar[i].first, ar[i].count = int(first), int(count)
+            ar[i].m[:] = [float(v) for v in m]
+        self._check(self._L.forma_hip_geometry_append(self._h, C.byref(ft), _p(ls), ar, len(affines)))
+        self.n_points += int(t["n_points"])
+
+    def geometry_append_paths(self, items):
+        """SegmentBuffer::push_path for every (path, slot) of `items`, in order: the host builds the paths' work items
+        (forma_host_batch_append), the device flattens them into the tail of the store."""
+        from .api import _host
+        H = _host()
+        batch = H.forma_host_batch_new()
+        try:
+            for path, slot in items:
+                H.forma_host_batch_add(batch, path._h, int(slot))
+            n = H.forma_host_batch_points(batch)
+            self._check(H.forma_host_batch_append(batch, self._h))
+        finally:
+            H.forma_host_batch_free(batch)
+        self.n_points += int(n)
+
+    def geometry_retain(self, keep, slot_remap):
+        """forma_hip_geometry_retain: keep = [(first point, count)] ascending and disjoint, slot_remap[old slot] = new slot or NONE"""
+        from ._lib import KeepRangeT
+        kr = (KeepRangeT * max(len(keep), 1))()
+        for i, (first, count) in enumerate(keep):
+            kr[i].first, kr[i].count = int(first), int(count)
+        rm = np.ascontiguousarray(slot_remap, np.uint32)
+        self._check(self._L.forma_hip_geometry_retain(self._h, kr, len(keep), _p(rm), len(rm)))
+        self.n_points = sum(int(c) for _, c in keep)
+
+    def read_geometry(self):
+        """forma_hip_read_geometry: (x, y, line_slot) of the store as forma_hip_set_geometry would have been given them"""
+        n = C.c_size_t(0)
+        rc = self._L.forma_hip_read_geometry(self._h, None, None, None, 0, C.byref(n))
+        if rc != 0 and rc != -4:
+            self._check(rc)
+        x = np.zeros(n.value, np.float32); y = np.zeros(n.value, np.float32); ls = np.zeros(max(n.value - 1, 0), np.uint32)
+        if n.value:
+            self._check(self._L.forma_hip_read_geometry(self._h, _p(x), _p(y), _p(ls), n.value, C.byref(n)))
+        return x, y, ls
+
+    def counters(self):
+        """forma_hip_counters as a dict: what the geometry edits cost and how the frames ran, since the context was created"""
+        from ._lib import CountersT
+        c = CountersT()
+        self._check(self._L.forma_hip_counters(self._h, C.byref(c)))
+        return c.as_dict()
+
     # ---- stages
     def flatten_tables(self, t):
         """forma_hip_flatten on caller-supplied work items (the fields of forma_flatten_tables_t as numpy arrays + n_points,

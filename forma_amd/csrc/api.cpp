@@ -1212,6 +1212,7 @@ void forma_hip_destroy(forma_hip_ctx* ctx) {
     if (ctx->h_xlocal) (void)hipHostFree(ctx->h_xlocal);
     if (ctx->h_written) (void)hipHostFree(ctx->h_written);
     if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
+    if (ctx->h_geo) (void)hipHostFree(ctx->h_geo);
     for (auto& c : ctx->caches) { c.tiles.release(); c.image.release(); }
     for (auto& r : ctx->registered) (void)hipHostUnregister(r.first);
     if (ctx->copy_stream) {
@@ -1238,9 +1239,12 @@ int forma_hip_set_geometry(forma_hip_ctx* ctx, const float* x, const float* y, c
     if ((rc = fd_drain(ctx))) return rc;                  // frames in flight still read the old buffers
     if ((rc = upload(ctx, ctx->x, x, n_points))) return rc;
     if ((rc = upload(ctx, ctx->y, y, n_points))) return rc;
-    if ((rc = upload(ctx, ctx->line_slot, line_slot, n_points ? n_points - 1 : 0))) return rc;
+    HIPCHECK(ctx->line_slot.ensure(std::max<size_t>(n_points, 1) * 4));   // (n_points entries: the store's last point starts no line,
+    if ((rc = upload(ctx, ctx->line_slot, line_slot, n_points ? n_points - 1 : 0))) return rc;   //  also once something is appended behind it)
+    if (n_points) HIPCHECK(hipMemsetAsync(ctx->line_slot.as<uint32_t>() + (n_points - 1), 0xFF, 4, ctx->stream));
     HIPCHECK(hipStreamSynchronize(ctx->stream));
     ctx->n_points = n_points;
+    ctx->cnt.geometry_uploads++; ctx->cnt.geometry_bytes_h2d += n_points * 8 + (n_points ? n_points - 1 : 0) * 4;
     invalidate_counts(ctx);                               // new geometry: the next frame re-learns N and J synchronously
     share_scene(ctx);
     return FORMA_OK;
@@ -1384,6 +1388,178 @@ int forma_hip_flatten(forma_hip_ctx* ctx, const forma_flatten_tables_t* t, float
     if (dx) (void)hipFree(dx);
     if (dy) (void)hipFree(dy);
     if (e != hipSuccess) return fail(ctx, FORMA_E_HIP, "flatten", e);
+    ctx->cnt.geometry_bytes_h2d += (3 * np + 16 * nq + 4 * ns) * 4; ctx->cnt.geometry_bytes_d2h += np * 8;
+    return FORMA_OK;
+}
+
+// ---- the geometry store as an incremental store ------------------------------------------------------------
+namespace {
+// the context's page-locked staging buffer (one append's work items, one retain's tables): grown geometrically, kept
+int geo_staging(forma_hip_ctx* ctx, size_t bytes) {
+    if (bytes <= ctx->h_geo_cap && ctx->h_geo) return FORMA_OK;
+    const size_t want = std::max<size_t>(std::max(bytes, ctx->h_geo_cap + ctx->h_geo_cap / 2), 4096);
+    if (ctx->h_geo) { (void)hipHostFree(ctx->h_geo); ctx->h_geo = nullptr; ctx->h_geo_cap = 0; }
+    HIPCHECK(hipHostMalloc((void**)&ctx->h_geo, want, hipHostMallocDefault));
+    ctx->h_geo_cap = want;
+    return FORMA_OK;
+}
+// an edit of the store, seen from the frame path: the line count and everything provisioned from it follow n_points at the
+// next frame (run_rasterize_frame, run_line_table); the predictions stay — N, J and the row / slice shapes are bounds a
+// read-back-free frame is checked against on the device (k_runs_count, k_frame_tail: plan_bad, N <= bN, J <= bJ), the key
+// masks, the layer order and the tile-field spans are verified there too, the bans, the painters' order lists, cull_on and the
+// measured slice length are hints — exactly what forma_hip_set_geoms relies on when a transform moves every line.  What cannot
+// stay is a fused frame's unsorted stream, which restore_unsorted would rebuild from the lines as they are NOW.
+void geometry_edited(forma_hip_ctx* ctx) {
+    if (ctx->seg_u_fused) { ctx->seg_u_fused = false; ctx->have_unsorted = false; }
+    for (forma_hip_ctx* sl : ctx->slots) if (sl->seg_u_fused) { sl->seg_u_fused = false; sl->have_unsorted = false; }
+    // (the bucket frames of the exchange layout size their buckets from the last local count: those plan anew, like the
+    //  multi-device context above them)
+    ctx->xpred_valid = false;
+    for (forma_hip_ctx* sl : ctx->slots) sl->xpred_valid = false;
+    ctx->cnt.geometry_points = ctx->n_points;
+    share_scene(ctx);
+}
+}  // namespace
+
+int forma_hip_geometry_append(forma_hip_ctx* ctx, const forma_flatten_tables_t* t, const uint32_t* line_slot,
+                              const forma_affine_range_t* affines, size_t n_affines) {
+    if (!ctx || !t) return fail(ctx, FORMA_E_ARG, "null flatten tables");
+    const size_t np = t->n_points, nq = t->n_quads, ns = t->n_splines;
+    if (np == 0) return FORMA_OK;
+    if (!line_slot || (n_affines && !affines)) return fail(ctx, FORMA_E_ARG, "null line_slot / affines");
+    if (!t->point_commands || !t->point_indices || !t->quad_indices) return fail(ctx, FORMA_E_ARG, "null flatten tables");
+    if (nq && (!t->qx || !t->qy || !t->qw || !t->x0 || !t->dx_recip || !t->k0 || !t->dk || !t->curvatures_recip || !t->partial_spline || !t->partial_curv))
+        return fail(ctx, FORMA_E_ARG, "null flatten tables");
+    if (ns && (!t->sp0x || !t->sp0y || !t->sp2x || !t->sp2y)) return fail(ctx, FORMA_E_ARG, "null flatten tables");
+    if (line_slot[np - 1] != FORMA_NONE) return fail(ctx, FORMA_E_ARG, "the last line slot of an append must be FORMA_NONE");
+    if (nq >= (1ull << 30) || ns >= (1ull << 30)) return fail(ctx, FORMA_E_ARG, "too many work items");
+    { uint64_t end = 0;
+      for (size_t i = 0; i < n_affines; i++) {
+          if (affines[i].first < end || affines[i].count > np || affines[i].first > np - affines[i].count)
+              return fail(ctx, FORMA_E_ARG, "affine ranges must be ascending, disjoint and inside the appended points");
+          end = affines[i].first + affines[i].count;
+      } }
+    if (ctx->multi) return multi_geometry_append(ctx, t, line_slot, affines, n_affines);
+    if (ctx->n_points + np >= (1ull << 30)) return fail(ctx, FORMA_E_ARG, "too many points");
+    HIPCHECK(hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = fd_drain(ctx))) return rc;                  // frames in flight still read the store (and it may move when it grows)
+    // ONE packed block: 4 words per point (3 work items + the line slot), 16 per quad (3 x 3 control values + 7 scalars), 4 per
+    // spline, 8 per affine range
+    const size_t words = 4 * np + (9 + 7) * nq + 4 * ns + 8 * n_affines;
+    const size_t bytes = words * 4;
+    if ((rc = geo_staging(ctx, bytes))) return rc;
+    HIPCHECK(ctx->geo_blob.ensure(bytes));
+    uint32_t* h = (uint32_t*)ctx->h_geo;
+    const uint32_t* d = ctx->geo_blob.as<uint32_t>();
+    forma_flatten_tables_t dt = *t;
+    size_t at = 0;
+    auto put = [&](const void* src, size_t n) -> const uint32_t* {
+        if (n) memcpy(h + at, src, n * 4);
+        const uint32_t* dev = d + at;
+        at += n;
+        return dev;
+    };
+    dt.point_commands = put(t->point_commands, np); dt.point_indices = put(t->point_indices, np); dt.quad_indices = put(t->quad_indices, np);
+    const uint32_t* d_slot = put(line_slot, np);
+    dt.qx = (const float*)put(t->qx, 3 * nq); dt.qy = (const float*)put(t->qy, 3 * nq); dt.qw = (const float*)put(t->qw, 3 * nq);
+    dt.x0 = (const float*)put(t->x0, nq); dt.dx_recip = (const float*)put(t->dx_recip, nq); dt.k0 = (const float*)put(t->k0, nq);
+    dt.dk = (const float*)put(t->dk, nq); dt.curvatures_recip = (const float*)put(t->curvatures_recip, nq);
+    dt.partial_spline = put(t->partial_spline, nq); dt.partial_curv = (const float*)put(t->partial_curv, nq);
+    dt.sp0x = (const float*)put(t->sp0x, ns); dt.sp0y = (const float*)put(t->sp0y, ns);
+    dt.sp2x = (const float*)put(t->sp2x, ns); dt.sp2y = (const float*)put(t->sp2y, ns);
+    const uint32_t* d_aff = d + at;
+    for (size_t i = 0; i < n_affines; i++) {
+        h[at] = (uint32_t)affines[i].first; h[at + 1] = (uint32_t)(affines[i].first + affines[i].count);
+        memcpy(h + at + 2, affines[i].m, 24);
+        at += 8;
+    }
+    // the store grows geometrically and keeps its contents
+    const size_t n_old = ctx->n_points, n_new = n_old + np;
+    HIPCHECK(ctx->x.grow_keep(n_new * 4, n_old * 4, ctx->stream));
+    HIPCHECK(ctx->y.grow_keep(n_new * 4, n_old * 4, ctx->stream));
+    HIPCHECK(ctx->line_slot.grow_keep(n_new * 4, n_old * 4, ctx->stream));
+    HIPCHECK(hipMemcpyAsync(ctx->geo_blob.p, h, bytes, hipMemcpyHostToDevice, ctx->stream));
+    GeomAppend A{(uint32_t)n_old, (uint32_t)n_affines, d_aff, d_slot, ctx->x.as<float>(), ctx->y.as<float>(), ctx->line_slot.as<uint32_t>()};
+    launch_flatten_store(ctx->stream, &dt, A);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(ctx->stream));          // (the staging buffer is free again; the frame slots' streams see the points)
+    ctx->n_points = n_new;
+    ctx->cnt.geometry_appends++; ctx->cnt.geometry_bytes_h2d += bytes;
+    geometry_edited(ctx);
+    return FORMA_OK;
+}
+
+int forma_hip_geometry_retain(forma_hip_ctx* ctx, const forma_keep_range_t* keep, size_t n_keep, const uint32_t* slot_remap, size_t n_slots) {
+    if (!ctx || (n_keep && !keep) || (n_slots && !slot_remap)) return fail(ctx, FORMA_E_ARG, "null keep ranges / slot remap");
+    if (n_slots > 0xFFFFFFFFull) return fail(ctx, FORMA_E_ARG, "too many slots");
+    if (ctx->multi) return multi_geometry_retain(ctx, keep, n_keep, slot_remap, n_slots);
+    HIPCHECK(hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = fd_drain(ctx))) return rc;
+    // the ranges: ascending, disjoint, inside the store; their destination offsets are the prefix sums of their lengths
+    uint64_t end = 0, n_out = 0;
+    size_t n_live = 0;
+    for (size_t i = 0; i < n_keep; i++) {
+        if (keep[i].first < end || keep[i].count > ctx->n_points || keep[i].first > ctx->n_points - keep[i].count)
+            return fail(ctx, FORMA_E_ARG, "keep ranges must be ascending, disjoint and inside the store");
+        end = keep[i].first + keep[i].count;
+        n_out += keep[i].count; n_live += keep[i].count ? 1 : 0;
+    }
+    const size_t bytes = (3 * n_live + n_slots) * 4;
+    if ((rc = geo_staging(ctx, std::max<size_t>(bytes, 4)))) return rc;
+    uint32_t* h = (uint32_t*)ctx->h_geo;
+    { uint32_t dst = 0; size_t k = 0;
+      for (size_t i = 0; i < n_keep; i++) {
+          if (!keep[i].count) continue;
+          h[3 * k] = (uint32_t)keep[i].first; h[3 * k + 1] = dst; h[3 * k + 2] = (uint32_t)keep[i].count;
+          dst += (uint32_t)keep[i].count; k++;
+      } }
+    if (n_slots) memcpy(h + 3 * n_live, slot_remap, n_slots * 4);
+    if (n_out) {
+        HIPCHECK(ctx->geo_blob.ensure(std::max<size_t>(bytes, 4)));
+        HIPCHECK(ctx->geo_flag.ensure(4));
+        for (DevBuf* b : {&ctx->x_spare, &ctx->y_spare, &ctx->line_slot_spare}) HIPCHECK(b->ensure(n_out * 4));
+        HIPCHECK(hipMemcpyAsync(ctx->geo_blob.p, h, bytes, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHECK(hipMemsetAsync(ctx->geo_flag.p, 0, 4, ctx->stream));
+        GeomRetain R{ctx->geo_blob.as<uint32_t>(), (uint32_t)n_live, ctx->geo_blob.as<uint32_t>() + 3 * n_live, (uint32_t)n_slots, (uint32_t)n_out,
+                     ctx->x.as<float>(), ctx->y.as<float>(), ctx->line_slot.as<uint32_t>(),
+                     ctx->x_spare.as<float>(), ctx->y_spare.as<float>(), ctx->line_slot_spare.as<uint32_t>(), ctx->geo_flag.as<uint32_t>()};
+        launch_geom_retain(ctx->stream, R);
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipMemcpyAsync(h, ctx->geo_flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHECK(hipStreamSynchronize(ctx->stream));
+        if (h[0]) return fail(ctx, FORMA_E_ARG, "the store holds a slot beyond the remap table");   // (nothing was swapped: the store is as it was)
+        std::swap(ctx->x, ctx->x_spare); std::swap(ctx->y, ctx->y_spare); std::swap(ctx->line_slot, ctx->line_slot_spare);
+    }
+    ctx->n_points = (size_t)n_out;
+    ctx->cnt.geometry_retains++; ctx->cnt.geometry_bytes_h2d += bytes;
+    geometry_edited(ctx);
+    return FORMA_OK;
+}
+
+int forma_hip_read_geometry(forma_hip_ctx* ctx, float* x, float* y, uint32_t* line_slot, size_t capacity_points, size_t* out_points) {
+    if (!ctx || !out_points) return fail(ctx, FORMA_E_ARG, "null out_points");
+    if (ctx->multi) ctx = multi_first(ctx);
+    const size_t n = ctx->n_points;
+    *out_points = n;
+    if (n > capacity_points) return fail(ctx, FORMA_E_CAPACITY, "geometry capacity too small");
+    if (n == 0) return FORMA_OK;
+    if (!x || !y || (n > 1 && !line_slot)) return fail(ctx, FORMA_E_ARG, "null geometry output");
+    HIPCHECK(hipSetDevice(ctx->device));
+    HIPCHECK(hipMemcpyAsync(x, ctx->x.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHECK(hipMemcpyAsync(y, ctx->y.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (n > 1) HIPCHECK(hipMemcpyAsync(line_slot, ctx->line_slot.p, (n - 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHECK(hipStreamSynchronize(ctx->stream));
+    ctx->cnt.geometry_bytes_d2h += n * 8 + (n - 1) * 4;
+    return FORMA_OK;
+}
+
+int forma_hip_counters(forma_hip_ctx* ctx, forma_counters_t* out) {
+    if (!ctx || !out) return FORMA_E_ARG;
+    if (ctx->multi) return multi_counters(ctx, out);
+    ctx->cnt.geometry_points = ctx->n_points;
+    *out = ctx->cnt;
     return FORMA_OK;
 }
 
@@ -1618,6 +1794,9 @@ int complete_async_frame(forma_hip_ctx* ctx, const PaintArgs& a, uint8_t* dst, s
     return rc;
 }
 
+// forma_hip_counters' frame counters live in the context the caller holds (a frame slot books on its owner)
+inline forma_counters_t& frame_counters(forma_hip_ctx* ctx) { return (ctx->owner ? ctx->owner : ctx)->cnt; }
+
 // the synchronous frame (first frame of a scene, or a prediction failed): N, the key masks and J are read back
 int render_sync(forma_hip_ctx* ctx, const PaintArgs& a, uint8_t* dst, size_t stride_bytes, bool timing, forma_timings_t* timings) {
     int rc;
@@ -1654,7 +1833,8 @@ int render_on(forma_hip_ctx* ctx, uint8_t* dst, const PaintArgs& a, size_t strid
         if ((rc = send_split_bands(ctx, dst, stride_bytes, a))) { (void)settle_split(ctx); return rc; }
         rc = complete_async_frame(ctx, a, dst, stride_bytes, timing, timings, bN, bJ);
         if (rc != FORMA_RETRY) return rc;
-    }
+        frame_counters(ctx).frames_rerun++;
+    } else frame_counters(ctx).frames_learned++;
     return render_sync(ctx, a, dst, stride_bytes, timing, timings);
 }
 
@@ -1667,7 +1847,7 @@ int settle_slot(forma_hip_ctx* sl) {
     const forma_hip_ctx::Deferred& d = sl->def;
     PaintArgs a{d.width, d.height, d.channels, d.clear, d.has_crop ? &d.crop : nullptr, -1, d.target, d.target_pitch, d.fmt};
     int rc = complete_async_frame(sl, a, d.dst, d.stride, false, nullptr, d.bN, d.bJ);
-    if (rc == FORMA_RETRY) rc = render_sync(sl, a, d.dst, d.stride, false, nullptr);
+    if (rc == FORMA_RETRY) { frame_counters(sl).frames_rerun++; rc = render_sync(sl, a, d.dst, d.stride, false, nullptr); }
     return rc;
 }
 
@@ -1730,6 +1910,7 @@ static int render_impl(forma_hip_ctx* ctx, uint8_t* dst, uint32_t width, uint32_
     int rc = check_paint_args(ctx, dst, width, height, stride_bytes, channels, clear_color);
     if (rc) return rc;
     if (cache_id >= 32) return fail(ctx, FORMA_E_ARG, "cache_id out of range");   // SmallBitSet u32, small_bit_set.rs:17-57
+    ctx->cnt.frames++;
     if (ctx->multi) return multi_render(ctx, dst, width, height, stride_bytes, channels, clear_color, crop_or_null, cache_id, timings);
     HIPCHECK(hipSetDevice(ctx->device));
     PaintArgs a{width, height, channels, clear_color, crop_or_null, cache_id, dt.target, dt.pitch, dt.fmt};
@@ -1764,6 +1945,7 @@ static int render_impl(forma_hip_ctx* ctx, uint8_t* dst, uint32_t width, uint32_
             }
         } else {
             if (dt.target && (rc = wait_for_caller(ctx, sl->stream, dt.wait))) return rc;
+            ctx->cnt.frames_learned++;
             rc = render_sync(sl, a, dst, stride_bytes, false, nullptr);
         }
         if (rc && sl != ctx) memcpy(ctx->err, sl->err, sizeof ctx->err);
@@ -2396,7 +2578,8 @@ int fd_gather_sort_paint(forma_hip_ctx* ctx, uint8_t* dst, uint32_t width, uint3
     if (enqueued) {
         rc = gsp_complete(ctx, g, bJ);
         if (rc != FORMA_RETRY) return rc;
-    }
+        ctx->cnt.frames_rerun++;
+    } else ctx->cnt.frames_learned++;
     return gsp_sync(ctx, g);
 }
 
@@ -2413,6 +2596,7 @@ int fd_gsp_defer(forma_hip_ctx* ctx, uint32_t width, uint32_t height, const uint
     bool enqueued = false;
     if ((rc = gsp_enqueue(ctx, g, &enqueued, &d.bJ))) return rc;
     if (enqueued) { ctx->xpending = true; return FORMA_OK; }
+    ctx->cnt.frames_learned++;
     return gsp_sync(ctx, g);
 }
 // ... and completed when the slot comes round again (or any call needs the result): FORMA_E_CAPACITY with ctx->xoverflowed when a
@@ -2424,7 +2608,7 @@ int fd_gsp_settle(forma_hip_ctx* ctx) {
     const forma_hip_ctx::Deferred& d = ctx->def;
     const GspArgs g{nullptr, d.width, d.height, 0, d.channels, d.clear, d.has_crop ? &d.crop : nullptr, -1, nullptr};
     int rc = gsp_complete(ctx, g, d.bJ);
-    if (rc == FORMA_RETRY) rc = gsp_sync(ctx, g);
+    if (rc == FORMA_RETRY) { ctx->cnt.frames_rerun++; rc = gsp_sync(ctx, g); }
     return rc;
 }
 

@@ -242,6 +242,27 @@ void launch_rasterize(hipStream_t s, const LineSource& src, DevCount n_compact, 
                       bool reduce_now /* false: the caller hands the records on as PendingMasks */,
                       const RasHist* hist = nullptr);
 void launch_flatten(hipStream_t s, const forma_flatten_tables_t* dev_tables, float* out_x, float* out_y);
+// the geometry store as an incremental store (forma_hip_geometry_append / _retain)
+struct GeomAppend {
+    uint32_t base;                   // points in the store before the append
+    uint32_t n_affines;
+    const uint32_t* affines;         // 8 words per range: first point, end point (exclusive), m[6] as f32 bits; ascending, disjoint
+    const uint32_t* slot_in;         // line slot per appended point
+    float* x; float* y; uint32_t* slot;   // the store
+};
+void launch_flatten_store(hipStream_t s, const forma_flatten_tables_t* dev_tables, const GeomAppend& A);
+constexpr uint32_t GR_THREADS = 256, GR_CHUNK = GR_THREADS * 4;
+struct GeomRetain {
+    const uint32_t* ranges;          // 3 words per kept range: first source point, first destination point, count (> 0)
+    uint32_t n_keep;
+    const uint32_t* remap;           // new slot (or FORMA_NONE) per old slot
+    uint32_t n_slots;
+    uint32_t n_out;                  // surviving points
+    const float* x; const float* y; const uint32_t* slot;
+    float* out_x; float* out_y; uint32_t* out_slot;
+    uint32_t* flag;                  // |= 1: a stored slot was >= n_slots
+};
+void launch_geom_retain(hipStream_t s, const GeomRetain& R);
 
 // sort.hip — stable LSB radix sort of u64 (chained-scan "onesweep" passes over the live key bits).
 #define SORT_MAX_PASSES 12

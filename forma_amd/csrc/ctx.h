@@ -30,6 +30,26 @@ struct DevBuf {
         }
         return e;
     }
+    // growth that KEEPS the first `used` bytes (the geometry store is appended to): a device-to-device copy into the new
+    // allocation on `s`, which is drained before the old one is freed; geometric like ensure
+    hipError_t grow_keep(size_t bytes, size_t used, hipStream_t s) {
+        if (bytes <= cap && p) return hipSuccess;
+        if (borrowed) return hipErrorInvalidValue;
+        size_t want = std::max(bytes, cap + cap / 2);
+        want = std::max<size_t>(want, 256);
+        void* q = nullptr;
+        hipError_t e = hipMalloc(&q, want);
+        if (e != hipSuccess) return e;
+        static const int poison = forma_debug_parse().poison;
+        if (poison >= 0) e = hipMemsetAsync(q, poison, want, s);
+        used = std::min(used, cap);
+        if (e == hipSuccess && p && used) e = hipMemcpyAsync(q, p, used, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { (void)hipFree(q); return e; }
+        if (p) (void)hipFree(p);
+        p = q; cap = want;
+        return hipSuccess;
+    }
     void release() { if (p && !borrowed) (void)hipFree(p); p = nullptr; cap = 0; borrowed = false; }
     void borrow(const DevBuf& o) { release(); p = o.p; cap = o.cap; borrowed = true; }
     template <class T> T* as() const { return (T*)p; }
@@ -51,6 +71,14 @@ struct forma_hip_ctx {
     DevBuf layer_sf, layer_col;             // per order: style summary for the carry pre-pass (set_styles)
     std::vector<uint32_t> h_layer_sf, h_layer_col;
     size_t n_points = 0, n_geoms = 0, n_orders = 0, n_words = 0, n_images = 0;
+    // the geometry store as an incremental store (forma_hip_geometry_append / _retain): line_slot holds n_points entries on
+    // the device, the last one FORMA_NONE (frames use n_points - 1 of them); retain compacts into the spare set and swaps
+    DevBuf x_spare, y_spare, line_slot_spare;
+    DevBuf geo_blob;                        // one append's work items / one retain's tables, as uploaded
+    DevBuf geo_flag;                        // k_geom_retain: a stored slot beyond the remap table
+    uint8_t* h_geo = nullptr;               // pinned staging of geo_blob (grown geometrically, kept); its first word receives geo_flag
+    size_t h_geo_cap = 0;
+    forma_counters_t cnt{};                 // forma_hip_counters (frame counters: kept by the owner of the frame slots)
     uint32_t max_geom_order = 0;            // largest order any geom slot names (FORMA_NONE slots aside)
     uint32_t max_image_index = 0;           // largest image index a texture style names
     bool any_texture = false;
@@ -226,7 +254,8 @@ struct forma_hip_ctx {
         &records, &rk_u, &rk_a, &rk_b, &blk_edge, &runs_scratch, &row_tab, &span_key, &span_cov, &ras_masks, &huge_offs, &huge_key, &huge_tmp,
         &huge_flag, &grp_tab, &grp_list, &run_lt, &rec_sp, &run_lt_sp, &row_sp, &pack_list, &pack_pix, &slice_buf}; }
     // released by trim, not refilled: parity line parameters, the scratch image (a cropped frame leaves the rest alone), exchange scratch, order lists
-    std::vector<DevBuf*> trimmed_bufs() { return {&l_order, &l_x0, &l_y0, &l_dx, &l_dy, &l_a, &l_b, &l_c, &l_d, &l_len, &image, &xscratch, &xmask, &order_buf}; }
+    std::vector<DevBuf*> trimmed_bufs() { return {&l_order, &l_x0, &l_y0, &l_dx, &l_dy, &l_a, &l_b, &l_c, &l_d, &l_len, &image, &xscratch, &xmask, &order_buf,
+        &x_spare, &y_spare, &line_slot_spare, &geo_blob, &geo_flag}; }
     // kept by trim, like the scene: FrameInfo and its template, cache frames' written-tile flags, the exchange's buckets
     std::vector<DevBuf*> kept_bufs() { return {&info, &info_init, &cache_written, &xsend, &xrecv}; }
 };
@@ -274,6 +303,10 @@ int  multi_create(forma_hip_ctx** out, const int* devices, int n);
 void multi_destroy(forma_hip_ctx* ctx);
 int  multi_set_geometry(forma_hip_ctx* ctx, const float* x, const float* y, const uint32_t* line_slot, size_t n_points);
 int  multi_set_geoms(forma_hip_ctx* ctx, const forma_geom_t* geoms, size_t n_geoms);
+int  multi_geometry_append(forma_hip_ctx* ctx, const forma_flatten_tables_t* t, const uint32_t* line_slot,
+                           const forma_affine_range_t* affines, size_t n_affines);
+int  multi_geometry_retain(forma_hip_ctx* ctx, const forma_keep_range_t* keep, size_t n_keep, const uint32_t* slot_remap, size_t n_slots);
+int  multi_counters(forma_hip_ctx* ctx, forma_counters_t* out);
 int  multi_set_styles(forma_hip_ctx* ctx, const uint32_t* style_offsets, size_t n_orders, const uint32_t* style_words,
                       size_t n_words, const uint8_t* unchanged);
 int  multi_set_images(forma_hip_ctx* ctx, const forma_image_t* images, size_t n_images, const uint16_t* texels, size_t n_texels);

@@ -365,6 +365,19 @@ int forma_host_batch_flatten(void* b_, forma_hip_ctx* ctx, float* out_x, float* 
     if (!b->line_slot.empty()) std::memcpy(out_line_slot, b->line_slot.data(), b->line_slot.size() * 4);
     return 0;
 }
+// stage 1 for the whole batch STRAIGHT INTO the tail of the context's geometry store (SegmentBuffer::push_path for every
+// path of the batch): work items, line slots and the paths' affine ranges go up in one block, nothing comes back
+int forma_host_batch_append(void* b_, forma_hip_ctx* ctx) {
+    FlattenBatch* b = (FlattenBatch*)b_;
+    forma_flatten_tables_t t;
+    b->tables(&t);
+    std::vector<forma_affine_range_t> ranges(b->affines.size());
+    for (size_t i = 0; i < ranges.size(); i++) {
+        ranges[i].first = b->affines[i].first; ranges[i].count = b->affines[i].count;
+        std::memcpy(ranges[i].m, b->affines[i].m, sizeof ranges[i].m);
+    }
+    return forma_hip_geometry_append(ctx, &t, b->line_slot.data(), ranges.data(), ranges.size());
+}
 // expose the work items (tests compare them with the oracle's flattener output through the kernel)
 void forma_host_batch_tables(void* b, forma_flatten_tables_t* t) { ((FlattenBatch*)b)->tables(t); }
 }

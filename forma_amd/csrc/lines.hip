@@ -968,33 +968,120 @@ __device__ __forceinline__ float inv_curvature(float k) {                       
     return k * (1.0f - C + sqrtf(fmaf(k * k, 0.25f, C * C)));
 }
 
+// one output point of into_segments: shared by k_flatten and k_flatten_store, so that a point appended to the store is
+// bit for bit the point a whole-scene flatten produces
+__device__ __forceinline__ void flatten_point(const forma_flatten_tables_t& t, size_t i, float& px, float& py) {
+    uint32_t cmd = t.point_commands[i];
+    if ((cmd & 0x7F800000u) == 0x7F800000u) {                       // PointCommand NaN-box, path.rs:137-168
+        uint32_t si = cmd & 0x3FFFFFu;
+        if ((cmd & 0x80000000u) == 0) { px = t.sp0x[si]; py = t.sp0y[si]; }      // Start
+        else { px = t.sp2x[si]; py = t.sp2y[si]; }                                // End
+    } else {
+        float incr = __uint_as_float(cmd);
+        uint32_t qi = t.quad_indices[i], pi = t.point_indices[i];
+        uint32_t spline_i = t.partial_spline[qi];
+        float prev = 0.0f;
+        if (qi >= 1 && t.partial_spline[qi - 1] == spline_i) prev = t.partial_curv[qi - 1];
+        float ratio = fmaf(incr, (float)pi, -prev) * t.curvatures_recip[qi];
+        float xx = inv_curvature(fmaf(ratio, t.dk[qi], t.k0[qi]));
+        float tt = (xx - t.x0[qi]) * t.dx_recip[qi];
+        if (tt < 0.0f) tt = 0.0f;
+        if (tt > 1.0f) tt = 1.0f;
+        size_t i0 = 3 * (size_t)qi, i1 = i0 + 1, i2 = i0 + 2;       // eval_quad path.rs:447-471
+        float w = lerpf(tt, lerpf(tt, t.qw[i0], t.qw[i1]), lerpf(tt, t.qw[i1], t.qw[i2]));
+        float wr = 1.0f / w;
+        px = lerpf(tt, lerpf(tt, t.qx[i0], t.qx[i1]), lerpf(tt, t.qx[i1], t.qx[i2])) * wr;
+        py = lerpf(tt, lerpf(tt, t.qy[i0], t.qy[i1]), lerpf(tt, t.qy[i1], t.qy[i2])) * wr;
+    }
+}
+
 __global__ __launch_bounds__(256) void k_flatten(forma_flatten_tables_t t, float* __restrict__ out_x,
                                                  float* __restrict__ out_y) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < t.n_points; i += (size_t)gridDim.x * blockDim.x) {
-        uint32_t cmd = t.point_commands[i];
         float px, py;
-        if ((cmd & 0x7F800000u) == 0x7F800000u) {                       // PointCommand NaN-box, path.rs:137-168
-            uint32_t si = cmd & 0x3FFFFFu;
-            if ((cmd & 0x80000000u) == 0) { px = t.sp0x[si]; py = t.sp0y[si]; }      // Start
-            else { px = t.sp2x[si]; py = t.sp2y[si]; }                                // End
-        } else {
-            float incr = __uint_as_float(cmd);
-            uint32_t qi = t.quad_indices[i], pi = t.point_indices[i];
-            uint32_t spline_i = t.partial_spline[qi];
-            float prev = 0.0f;
-            if (qi >= 1 && t.partial_spline[qi - 1] == spline_i) prev = t.partial_curv[qi - 1];
-            float ratio = fmaf(incr, (float)pi, -prev) * t.curvatures_recip[qi];
-            float xx = inv_curvature(fmaf(ratio, t.dk[qi], t.k0[qi]));
-            float tt = (xx - t.x0[qi]) * t.dx_recip[qi];
-            if (tt < 0.0f) tt = 0.0f;
-            if (tt > 1.0f) tt = 1.0f;
-            size_t i0 = 3 * (size_t)qi, i1 = i0 + 1, i2 = i0 + 2;       // eval_quad path.rs:447-471
-            float w = lerpf(tt, lerpf(tt, t.qw[i0], t.qw[i1]), lerpf(tt, t.qw[i1], t.qw[i2]));
-            float wr = 1.0f / w;
-            px = lerpf(tt, lerpf(tt, t.qx[i0], t.qx[i1]), lerpf(tt, t.qx[i1], t.qx[i2])) * wr;
-            py = lerpf(tt, lerpf(tt, t.qy[i0], t.qy[i1]), lerpf(tt, t.qy[i1], t.qy[i2])) * wr;
-        }
+        flatten_point(t, i, px, py);
         out_x[i] = px; out_y[i] = py;
+    }
+}
+
+// flatten straight into the tail of the geometry store (SegmentBuffer::push_path, segment.rs:180-198): into_segments writing at
+// store + base, the per-range GeomPresTransform of Path::push_segments_to (path.rs:689-706) applied by the same thread — the
+// range of a point is found by binary search over the ascending range table — and the point's line slot stored with it.
+__global__ __launch_bounds__(256) void k_flatten_store(forma_flatten_tables_t t, GeomAppend A) {
+    const uint32_t n = (uint32_t)t.n_points;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        float px, py;
+        flatten_point(t, i, px, py);
+        uint32_t lo = 0, hi = A.n_affines;                          // first range that ends behind i
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (A.affines[8 * mid + 1] <= i) lo = mid + 1; else hi = mid;
+        }
+        if (lo < A.n_affines && A.affines[8 * lo] <= i) {
+            const float* m = (const float*)(A.affines + 8 * lo + 2);
+            const float ax = fmaf(m[0], px, fmaf(m[2], py, m[4]));
+            const float ay = fmaf(m[1], px, fmaf(m[3], py, m[5]));
+            px = ax; py = ay;
+        }
+        A.x[A.base + i] = px; A.y[A.base + i] = py; A.slot[A.base + i] = A.slot_in[i];
+    }
+}
+
+// SegmentBuffer::retain (segment.rs:237-273): a stable segmented copy of x, y and the line slots through the keep table, the
+// slots renumbered through `remap`.  A streaming kernel, 24 bytes per surviving point.  A workgroup owns GR_CHUNK consecutive
+// OUTPUT points per step (a lane four of them): it finds the chunk's first range by binary search over the ranges' destination
+// offsets (the host's prefix sums), each lane walks on from there.  Four points go as one 16-byte access wherever they lie in
+// one range and the source is aligned like the destination; else point by point.
+__global__ __launch_bounds__(GR_THREADS) void k_geom_retain(GeomRetain R) {
+    const uint32_t n_chunks = (R.n_out + GR_CHUNK - 1) / GR_CHUNK;
+    for (uint32_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+        const uint32_t o0 = c * GR_CHUNK;
+        uint32_t lo = 0, hi = R.n_keep;                             // ranges[lo].dst <= o0 < ranges[hi].dst (range 0 starts at 0)
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (R.ranges[3 * mid + 1] <= o0) lo = mid; else hi = mid;
+        }
+        const uint32_t o = o0 + threadIdx.x * 4u;
+        if (o >= R.n_out) continue;
+        uint32_t r = lo;
+        while (r + 1 < R.n_keep && R.ranges[3 * (r + 1) + 1] <= o) r++;
+        uint32_t src = R.ranges[3 * r] + (o - R.ranges[3 * r + 1]);
+        uint32_t left = R.ranges[3 * r + 1] + R.ranges[3 * r + 2] - o;      // points of range r from o on (>= 1: ranges are not empty)
+        const uint32_t m = min(4u, R.n_out - o);
+        float vx[4], vy[4]; uint32_t vs[4];
+        if (m == 4u && left >= 4u && (src & 3u) == 0u) {
+            const float4 a = *(const float4*)(R.x + src), b = *(const float4*)(R.y + src);
+            const uint4 s4 = *(const uint4*)(R.slot + src);
+            vx[0] = a.x; vx[1] = a.y; vx[2] = a.z; vx[3] = a.w;  vy[0] = b.x; vy[1] = b.y; vy[2] = b.z; vy[3] = b.w;
+            vs[0] = s4.x; vs[1] = s4.y; vs[2] = s4.z; vs[3] = s4.w;
+        } else {
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; k++) {
+                vx[k] = 0.0f; vy[k] = 0.0f; vs[k] = FORMA_NONE;
+                if (k < m) {
+                    if (left == 0u) { r++; src = R.ranges[3 * r]; left = R.ranges[3 * r + 2]; }
+                    vx[k] = R.x[src]; vy[k] = R.y[src]; vs[k] = R.slot[src];
+                    src++; left--;
+                }
+            }
+        }
+        bool bad = false;
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; k++)
+            if (vs[k] != FORMA_NONE) {
+                if (vs[k] < R.n_slots) vs[k] = R.remap[vs[k]];
+                else { bad = true; vs[k] = FORMA_NONE; }
+            }
+        if (bad) atomicOr(R.flag, 1u);                              // (the host then leaves the store as it was)
+        if (m == 4u) {
+            *(float4*)(R.out_x + o) = make_float4(vx[0], vx[1], vx[2], vx[3]);
+            *(float4*)(R.out_y + o) = make_float4(vy[0], vy[1], vy[2], vy[3]);
+            *(uint4*)(R.out_slot + o) = make_uint4(vs[0], vs[1], vs[2], vs[3]);
+        } else {
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; k++)
+                if (k < m) { R.out_x[o + k] = vx[k]; R.out_y[o + k] = vy[k]; R.out_slot[o + k] = vs[k]; }
+        }
     }
 }
 
@@ -1003,4 +1090,18 @@ void launch_flatten(hipStream_t s, const forma_flatten_tables_t* dev_tables, flo
     size_t blocks = (dev_tables->n_points + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     FORMA_LAUNCH(k_flatten, dim3((uint32_t)blocks), dim3(256), 0, s, *dev_tables, out_x, out_y);
+}
+
+void launch_flatten_store(hipStream_t s, const forma_flatten_tables_t* dev_tables, const GeomAppend& A) {
+    if (dev_tables->n_points == 0) return;
+    size_t blocks = (dev_tables->n_points + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    FORMA_LAUNCH(k_flatten_store, dim3((uint32_t)blocks), dim3(256), 0, s, *dev_tables, A);
+}
+
+void launch_geom_retain(hipStream_t s, const GeomRetain& R) {
+    if (R.n_out == 0) return;
+    size_t blocks = ((size_t)R.n_out + GR_CHUNK - 1) / GR_CHUNK;
+    if (blocks > 2048) blocks = 2048;                              // (8 workgroups per CU; the rest of the output by grid stride)
+    FORMA_LAUNCH(k_geom_retain, dim3((uint32_t)blocks), dim3(GR_THREADS), 0, s, R);
 }

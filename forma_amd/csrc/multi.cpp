@@ -748,6 +748,34 @@ int multi_set_geometry(forma_hip_ctx* ctx, const float* x, const float* y, const
     EACH_KID(fd_set_line_range(k, false, 0, 0));
     return FORMA_OK;
 }
+// an edit of the store goes to every device (each flattens the appended paths itself: the same kernel on the same work items);
+// line shares and bands depend on the line count, so the next frame plans anew
+int multi_geometry_append(forma_hip_ctx* ctx, const forma_flatten_tables_t* t, const uint32_t* line_slot,
+                          const forma_affine_range_t* affines, size_t n_affines) {
+    MULTI_ENTER();
+    if (ctx->multi->kid[0]->n_points + t->n_points >= (1ull << 30)) return MFAIL(FORMA_E_ARG, "too many points");
+    ctx->multi->planned = false;
+    EACH_KID(forma_hip_geometry_append(k, t, line_slot, affines, n_affines));
+    EACH_KID(fd_set_line_range(k, false, 0, 0));
+    return FORMA_OK;
+}
+int multi_geometry_retain(forma_hip_ctx* ctx, const forma_keep_range_t* keep, size_t n_keep, const uint32_t* slot_remap, size_t n_slots) {
+    MULTI_ENTER();
+    // (a refused call leaves every device's store as it was: the devices hold the same store and refuse alike, the first one first)
+    EACH_KID(forma_hip_geometry_retain(k, keep, n_keep, slot_remap, n_slots));
+    ctx->multi->planned = false;
+    EACH_KID(fd_set_line_range(k, false, 0, 0));
+    return FORMA_OK;
+}
+int multi_counters(forma_hip_ctx* ctx, forma_counters_t* out) {
+    MultiState* M = ctx->multi;
+    *out = M->kid[0]->cnt;
+    out->geometry_points = M->kid[0]->n_points;
+    out->frames = ctx->cnt.frames;                         // (the calls the context saw; a re-planned frame runs twice on the devices)
+    out->geometry_bytes_h2d = 0; out->geometry_bytes_d2h = 0;
+    for (int g = 0; g < M->G; g++) { out->geometry_bytes_h2d += M->kid[g]->cnt.geometry_bytes_h2d; out->geometry_bytes_d2h += M->kid[g]->cnt.geometry_bytes_d2h; }
+    return FORMA_OK;
+}
 int multi_set_geoms(forma_hip_ctx* ctx, const forma_geom_t* geoms, size_t n_geoms) {
     // (transforms move segments between bands: the plan stays — its capacity carries 6 % slack and a frame that outgrows it
     //  re-plans; a layer that is switched on or off changes far less than that in practice)

@@ -191,6 +191,49 @@ typedef struct forma_flatten_tables_t {
 int forma_hip_flatten(forma_hip_ctx* ctx, const forma_flatten_tables_t* t,
                       float* out_x, float* out_y);
 
+/* ---- the geometry store as an incremental store (reference SegmentBuffer::push_path / retain) -- */
+/* forma_hip_set_geometry replaces the store; these two edit it in place, at a cost proportional to the edit.
+ * The invariant: after any sequence of set_geometry / append / retain the device arrays are bit for bit what
+ * forma_hip_set_geometry would hold after flattening the surviving pushes from scratch (forma_hip_flatten + the host's
+ * per-point affines), in the same order and with the same slot numbers.  Frames in flight are finished first.  On a
+ * single-device context neither call invalidates the predictions of the read-back-free frame path: the frame after an
+ * edit is enqueued like any other and verified on the device (a frame that outgrew its bounds is voided and rendered
+ * again).  On a multi-device context the calls go to every device and the next frame plans anew. */
+typedef struct forma_affine_range_t { uint64_t first, count; float m[6]; } forma_affine_range_t;
+typedef struct forma_keep_range_t   { uint64_t first, count; } forma_keep_range_t;
+/* Flatten `t` on the device straight into the tail of the store (SegmentBuffer::push_path, segment.rs:180-198); nothing is
+ * copied back.  line_slot has t->n_points entries and its last one must be FORMA_NONE (push_path ends every path with
+ * None).  affines: ascending disjoint point ranges of `t` that carry a GeomPresTransform (path.rs:689-706), applied on the
+ * device with the host's arithmetic: x' = fmaf(m0, x, fmaf(m2, y, m4)), y' = fmaf(m1, x, fmaf(m3, y, m5)).
+ * All work items travel as one packed block from a page-locked staging buffer of the context; once that buffer and the
+ * store have reached their sizes the call allocates nothing and waits for the device once.  0 points: no-op.
+ * FORMA_E_ARG: a last slot that is not FORMA_NONE, ranges out of order / overlapping / beyond t->n_points, a store that
+ * would reach 2^30 points. */
+int forma_hip_geometry_append(forma_hip_ctx* ctx, const forma_flatten_tables_t* t, const uint32_t* line_slot,
+                              const forma_affine_range_t* affines, size_t n_affines);
+/* SegmentBuffer::retain (segment.rs:237-273): `keep` lists ascending disjoint point ranges (whole pushes) that survive,
+ * order preserved; slot_remap[old slot] = new slot or FORMA_NONE, n_slots entries.  The store is compacted into a second
+ * set of buffers which then takes its place (forma_hip_trim releases the spare set).  FORMA_E_ARG — and the store is left
+ * as it was — for ranges out of order, overlapping or beyond the store, and for a stored slot >= n_slots. */
+int forma_hip_geometry_retain(forma_hip_ctx* ctx, const forma_keep_range_t* keep, size_t n_keep,
+                              const uint32_t* slot_remap, size_t n_slots);
+/* Inspection: what forma_hip_set_geometry would have been given for the store as it is: *out_points = n points in x / y,
+ * n - 1 line slots.  FORMA_E_CAPACITY (with *out_points set) if capacity_points is too small.  A multi-device context
+ * answers from its first device. */
+int forma_hip_read_geometry(forma_hip_ctx* ctx, float* x, float* y, uint32_t* line_slot,
+                            size_t capacity_points, size_t* out_points);
+/* Monotonic counters since forma_hip_create: what an edit cost, and how the frames behind it ran.  A multi-device context
+ * reports its first device's, with the byte counters summed over the devices. */
+typedef struct forma_counters_t {
+    uint64_t geometry_points;                          /* points in the store now */
+    uint64_t geometry_uploads, geometry_appends, geometry_retains;   /* set_geometry / append / retain calls that changed the store */
+    uint64_t geometry_bytes_h2d, geometry_bytes_d2h;   /* geometry and flatten work items only */
+    uint64_t frames;                                   /* frames rendered */
+    uint64_t frames_learned;                           /* synchronous frames: no valid prediction of N, key masks, J */
+    uint64_t frames_rerun;                             /* read-back-free frames voided on the device and rendered again */
+} forma_counters_t;
+int forma_hip_counters(forma_hip_ctx* ctx, forma_counters_t* out);
+
 /* ---- stage entry points for parity tests (host arrays in, host arrays out) ----------------- */
 /* prepare_lines = SegmentBuffer::fill_cpu_view (segment.rs:275-402) on the uploaded geometry.
  * Each output array has n_points-1 entries; `lengths` holds the INCLUSIVE prefix sums exactly

@@ -144,6 +144,38 @@ pub struct forma_context_info_t {
     pub devices: [i32; FORMA_MAX_DEVICES],
 }
 
+/// `forma_affine_range_t`: a point range of an append that carries a `GeomPresTransform` (`path.rs:689-706`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct forma_affine_range_t {
+    pub first: u64,
+    pub count: u64,
+    pub m: [f32; 6],
+}
+
+/// `forma_keep_range_t`: a point range (whole pushes) that survives `forma_hip_geometry_retain`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct forma_keep_range_t {
+    pub first: u64,
+    pub count: u64,
+}
+
+/// `forma_counters_t`: monotonic counters since `forma_hip_create` (what the geometry edits cost, how the frames ran).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct forma_counters_t {
+    pub geometry_points: u64,
+    pub geometry_uploads: u64,
+    pub geometry_appends: u64,
+    pub geometry_retains: u64,
+    pub geometry_bytes_h2d: u64,
+    pub geometry_bytes_d2h: u64,
+    pub frames: u64,
+    pub frames_learned: u64,
+    pub frames_rerun: u64,
+}
+
 /// `forma_kernel_time_t` (`include/forma_hip.h`): one kernel of the last timed frame, timed by its own launch events.
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -209,6 +241,31 @@ extern "C" {
         out_x: *mut f32,
         out_y: *mut f32,
     ) -> c_int;
+
+    // the geometry store as an incremental store (SegmentBuffer::push_path / retain)
+    pub fn forma_hip_geometry_append(
+        ctx: *mut forma_hip_ctx,
+        t: *const forma_flatten_tables_t,
+        line_slot: *const u32,
+        affines: *const forma_affine_range_t,
+        n_affines: usize,
+    ) -> c_int;
+    pub fn forma_hip_geometry_retain(
+        ctx: *mut forma_hip_ctx,
+        keep: *const forma_keep_range_t,
+        n_keep: usize,
+        slot_remap: *const u32,
+        n_slots: usize,
+    ) -> c_int;
+    pub fn forma_hip_read_geometry(
+        ctx: *mut forma_hip_ctx,
+        x: *mut f32,
+        y: *mut f32,
+        line_slot: *mut u32,
+        capacity_points: usize,
+        out_points: *mut usize,
+    ) -> c_int;
+    pub fn forma_hip_counters(ctx: *mut forma_hip_ctx, out: *mut forma_counters_t) -> c_int;
 
     // stage entry points (parity tests)
     pub fn forma_hip_prepare_lines(

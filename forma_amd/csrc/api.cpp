@@ -401,20 +401,6 @@ int verify_speculation(forma_hip_ctx* ctx) {
     return wrong ? FORMA_RETRY : FORMA_OK;
 }
 
-struct PaintArgs {
-    uint32_t width, height;
-    const uint8_t* channels;
-    const float* clear;
-    const forma_rect_t* crop;
-    int cache_id = -1;
-    // forma_hip_render_device: the painters write straight into the caller's device memory (pitch in bytes, FORMA_FORMAT_*);
-    // nullptr: into the context's scratch image or the cache's own image, as RGBA8
-    uint8_t* target = nullptr;
-    size_t target_pitch = 0;
-    uint32_t fmt = FORMA_FORMAT_SRGB8;
-    uint32_t tiles_w() const { return (width + 15) / 16; }  uint32_t tiles_h() const { return (height + 15) / 16; }
-};
-
 // the frame's crop in tiles, clamped to the tile rectangle [x0, x1) x [y0, y1) of the canvas (Rect::new, renderer.rs:43-52)
 struct TileRect { uint32_t x0, x1, y0, y1; };
 TileRect crop_tiles(const PaintArgs& a) {
@@ -426,7 +412,7 @@ TileRect crop_tiles(const PaintArgs& a) {
 // of kernels.  Painted in bands of tile rows — one launch and one event per band — the first band's pixels leave after an
 // eighth of the painter instead, on a second stream, and the link is busy while the rest is painted (the copies then end ~70 us
 // earlier; what the bands cost the painter — no heavy-first order across launches, eight tails — hides under the copy).
-// Only read-back-free frames of render_on that deliver into `dst` ask for it (split_want), never with a cache (the written-tile
+// Only read-back-free frames that enqueue_own verifies at once and that deliver into `dst` ask for it (split_want), never with a cache (the written-tile
 // set decides what is copied) and not for images of a few MB.  Returns the number of bands, 0: one launch as ever.
 #define SPLIT_MIN_RUNS 262144u
 int split_plan(forma_hip_ctx* ctx, const PaintArgs& a, const PaintParams& P, uint32_t bound_j, bool timing) {
@@ -837,7 +823,7 @@ int run_paint(forma_hip_ctx* ctx, DevCount nc, const PaintArgs& a, bool timing, 
     if (jc.bound > 0) launch_carry(ctx, a, P, tab, cp, nc, jc, groups, sorted_keys);
     stage_end(ctx, ST_CARRY, timing);
     stage_begin(ctx, ST_PAINT, timing);
-    // the painter in bands of tile rows, an event behind each (render_on sends their pixels out behind those) — or as one band
+    // the painter in bands of tile rows, an event behind each (enqueue_own sends their pixels out behind those) — or as one band
     const int bands = split_n > 1 && !launch_deep ? split_n : 1;
     ctx->split_n = 0;
     ctx->split_row[0] = P.crop_y0; ctx->split_row[bands] = P.crop_y1;
@@ -1093,6 +1079,33 @@ void clear_stage_flags(forma_hip_ctx* ctx) {
     for (int s = 0; s < ST_COUNT; s++) ctx->stage_used[s] = false;
     ctx->kt.n = 0; ctx->kt.dropped = 0; g_ktimer = nullptr;
     ctx->order_cnt_dev = nullptr; ctx->order_keep_dev = nullptr;       // (a frame that never reached its k_frame_tail)
+}
+
+// How every frame ends once its kernels are on the stream: FrameInfo on the host, the over-deep tiles painted, the image in
+// caller memory (and landed there when the call returns), timings resolved, the clear colour remembered in the cache.
+//   info_on_host: k_frame_tail brought FrameInfo (a read-back-free frame, already waited for); else it is read back now.
+//   early_image:  the frame's image may have left before it was verified (a deferred frame into caller memory, a split frame's
+//                 bands: image_sent / split_sent) — own-geometry read-back-free frames only.
+int deliver(forma_hip_ctx* ctx, const FrameRequest& r, bool info_on_host, bool early_image) {
+    const PaintArgs a = r.paint();
+    int rc;
+    if (!info_on_host && (rc = read_info(ctx))) return rc;
+    // (an image that left speculatively behind its kernels stays where it is; tiles that k_paint_huge paints only now: the crop
+    //  is copied again)
+    bool in_place = false, was_split = false;
+    if (early_image) {
+        in_place = ctx->image_sent && !(ctx->h_info->error & 8u);
+        was_split = ctx->split_sent;
+        if ((rc = settle_split(ctx))) return rc;           // (a split frame: its bands have landed — or land before the crop is copied again)
+    }
+    if ((rc = finish_paint(ctx))) return rc;
+    if ((rc = copy_image_out(ctx, r.dst, r.stride, r.timing(), a, in_place))) return rc;
+    if (r.dst && !(was_split && in_place)) HIPCHECK(hipStreamSynchronize(ctx->stream));   // (split: the tail has run, the copy stream is drained)
+    rc = finish_frame(ctx, r.timings, true);
+    if (rc == FORMA_OK && a.cache_id >= 0) {               // renderer.rs:217-218: remember the clear colour in the cache
+        ctx->caches[a.cache_id].has_clear = true; memcpy(ctx->caches[a.cache_id].clear, a.clear, 16);
+    }
+    return rc;
 }
 
 int check_paint_args(forma_hip_ctx* ctx, uint8_t* dst, uint32_t width, uint32_t height, size_t stride,
@@ -1675,22 +1688,15 @@ int forma_hip_paint(forma_hip_ctx* ctx, const uint64_t* sorted_segments, size_t 
     ctx->sorted = ctx->seg_a.as<uint64_t>();
     ctx->n_seg = n; ctx->have_unsorted = false;
     ctx->live44 = n ? host_live44(sorted_segments, n) : 0;
-    PaintArgs a{width, height, channels, clear_color, crop_or_null};
-    if ((rc = run_paint(ctx, DevCount{nullptr, (uint32_t)n}, a, false))) return rc;
-    if ((rc = read_info(ctx)) || (rc = finish_paint(ctx))) return rc;
-    if ((rc = copy_image_out(ctx, dst, stride_bytes, false, a))) return rc;
-    if (dst) HIPCHECK(hipStreamSynchronize(ctx->stream));
-    return finish_frame(ctx, nullptr, true);
+    const FrameRequest r(dst, width, height, stride_bytes, channels, clear_color, crop_or_null, -1, nullptr);
+    if ((rc = run_paint(ctx, DevCount{nullptr, (uint32_t)n}, r.paint(), false))) return rc;
+    return deliver(ctx, r, false, false);
 }
 
 // ---- the frame ---------------------------------------------------------------------------------------
 }  // extern "C"
 
 namespace {
-
-void frame_done(forma_hip_ctx* ctx, int rc, const PaintArgs& a) {      // renderer.rs:217-218: remember the clear colour in the cache
-    if (rc == FORMA_OK && a.cache_id >= 0) { ctx->caches[a.cache_id].has_clear = true; memcpy(ctx->caches[a.cache_id].clear, a.clear, 16); }
-}
 
 // FORMA_HIP_POISON_FRAME=<byte> (tests, tools): every per-frame buffer is refilled with that byte when a frame starts.  Frames of
 // a test re-render one scene, so a kernel that reads what THIS frame never wrote normally finds last frame's (identical,
@@ -1704,11 +1710,30 @@ int poison_frame_buffers(forma_hip_ctx* c) {
     return FORMA_OK;
 }
 
-// A read-back-free frame, first half: everything is enqueued on the context's stream, nothing waits.  N, J and the sort
-// plan are predicted from the previous frame (bounds with slack); device-side guards keep a wrong guess memory-safe.
-int enqueue_async_frame(forma_hip_ctx* ctx, const PaintArgs& a, bool timing, uint32_t* bN_out, uint32_t* bJ_out) {
-    const uint32_t bN = ctx->pred_N + ctx->pred_N / 16 + 4096, bJ = ctx->pred_J + ctx->pred_J / 16 + 4096;
-    *bN_out = bN; *bJ_out = bJ;
+// ---- one lifecycle for every frame: ENQUEUED read-back-free when the context has predictions, VERIFIED when somebody needs it,
+//      RUN AGAIN synchronously when a prediction was wrong — or synchronous at once, which learns the predictions — and
+//      DELIVERED (deliver, above) either way.  What produces the frame's sorted stream is the FRONT: the context's own geometry
+//      (OWN_GEOMETRY, below) or the buckets received through the exchange (RECEIVED, with the exchange entry points).
+struct Front {
+    // read-back-free: everything up to k_frame_tail goes onto the stream, nothing waits; r.bN / r.bJ are set.  parked != nullptr:
+    // the frame stays in flight (r is the slot's parked request); set as soon as the frame's kernels are on the stream
+    int (*enqueue)(forma_hip_ctx*, FrameRequest& r, bool* parked);
+    // synchronous: ctx->sorted holds the sorted stream, its count ctx->n_seg and the key masks have been read back
+    int (*produce)(forma_hip_ctx*, const FrameRequest& r, bool first_attempt);
+    // The stream came through the exchange.  Such a frame is waited for on its stream and reports a bucket that outgrew the plan
+    // before anything is judged; its N is not this context's own count (verdict); nothing of it leaves early (deliver); and its
+    // counters are booked on the context it ran on, frame slot or not (multi_counters reports the first slot's)
+    bool received;
+};
+
+// forma_hip_counters' frame counters live in the context the caller holds (a frame slot books on its owner)
+inline forma_counters_t& frame_counters(forma_hip_ctx* ctx, const Front& f) { return (ctx->owner && !f.received ? ctx->owner : ctx)->cnt; }
+
+inline bool may_enqueue(const forma_hip_ctx* ctx) { return ctx->pred_valid && ctx->pred_counts_valid && !ctx->no_async; }
+
+// The front of the context's own geometry, read-back-free: N, J and the sort plan are predicted from the previous frame (bounds
+// with slack); device-side guards keep a wrong guess memory-safe.
+int enqueue_own_kernels(forma_hip_ctx* ctx, const PaintArgs& a, bool timing, uint32_t bN, uint32_t bJ) {
     FrameInfo* dinfo = ctx->info.as<FrameInfo>();
     int rc;
     if ((rc = poison_frame_buffers(ctx))) return rc;
@@ -1724,9 +1749,37 @@ int enqueue_async_frame(forma_hip_ctx* ctx, const PaintArgs& a, bool timing, uin
     if (rc) return rc;
     return frame_tail(ctx, true, nullptr);
 }
+int enqueue_own(forma_hip_ctx* ctx, FrameRequest& r, bool* parked) {
+    const PaintArgs a = r.paint();
+    r.bN = ctx->pred_N + ctx->pred_N / 16 + 4096; r.bJ = ctx->pred_J + ctx->pred_J / 16 + 4096;
+    ctx->split_want = !parked && r.dst && !r.timing();    // (into caller memory and verified at once: the painter may run in bands, run_paint)
+    ctx->split_n = 0;
+    ctx->frame_has_dst = parked && r.dst;                 // (sort_workgroups: such a frame's digit passes keep the whole chip)
+    int rc = enqueue_own_kernels(ctx, a, r.timing(), r.bN, r.bJ);
+    ctx->split_want = false; ctx->frame_has_dst = false;
+    if (rc) return rc;
+    if (!parked) {
+        if ((rc = send_split_bands(ctx, r.dst, r.stride, a))) (void)settle_split(ctx);
+        return rc;
+    }
+    *parked = true;
+    if (r.dst) {
+        // the image leaves speculatively, in one piece behind the frame's kernels (verified at settle time; a void frame
+        // is run again into `dst`): it crosses PCIe while the NEXT frames are rasterized, sorted and painted
+        rc = copy_image_out(ctx, r.dst, r.stride, false, a);
+        ctx->image_sent = rc == FORMA_OK;
+    }
+    return rc;
+}
+// ... and synchronous (first frame of a scene, or a prediction failed): N, the key masks and J are read back
+int produce_own(forma_hip_ctx* ctx, const FrameRequest& r, bool first_attempt) {
+    int rc;
+    if ((rc = poison_frame_buffers(ctx))) return rc;
+    if ((rc = run_rasterize_frame(ctx, r.width, r.height, r.timing(), /*speculate=*/first_attempt))) return rc;
+    return run_sort(ctx, ctx->seg_u.as<uint64_t>(), DevCount{nullptr, (uint32_t)ctx->n_seg}, r.timing());
+}
+constexpr Front OWN_GEOMETRY{enqueue_own, produce_own, false};
 
-// ... second half: wait, verify.  FORMA_RETRY: a prediction failed, nothing of the frame may be used (the caller re-runs it
-// synchronously).  The frame is verified BEFORE anything lands in caller memory: a mispredicted frame never shows in `dst`.
 // The end of a read-back-free frame as the host sees it.  k_frame_tail writes the frame's number into pinned memory behind the
 // FrameInfo (system-scope release): polling that word returns a few microseconds before hipStreamSynchronize would — the stream's
 // completion signal takes the runtime's wake-up path — and the frame's kernels are all complete when its last one has stored.
@@ -1745,111 +1798,115 @@ int wait_frame_tail(forma_hip_ctx* ctx, bool timing) {
     return FORMA_OK;
 }
 
-int complete_async_frame(forma_hip_ctx* ctx, const PaintArgs& a, uint8_t* dst, size_t stride_bytes, bool timing,
-                         forma_timings_t* timings, uint32_t bN, uint32_t bJ) {
-    { const int wrc = wait_frame_tail(ctx, timing); if (wrc) return wrc; }
-    const uint32_t N = ctx->h_info->n_segments, J = ctx->h_info->n_runs;
-    ctx->n_seg = N; ctx->n_compact = ctx->h_info->n_compact; ctx->last_runs = J;
-    const bool ok = !ctx->h_info->plan_bad && N <= bN && J <= bJ;
-    if (!ok) {
-        { const int src = settle_split(ctx); if (src) return src; }               // (a split frame's bands are on their way: the re-run writes `dst` again)
-        if (ctx->small_tried && ctx->h_info->plan_bad) ctx->small_banned = true;   // (one cause of plan_bad: a slice beyond the small variant)
-        if (ctx->covl_tried && ctx->h_info->plan_bad) ctx->covl_banned = true;     // (another: a row beyond the COVL carry variant's LDS)
-        if (ctx->plan_biased && ctx->h_info->plan_bad) ban_bias(ctx);              // (another: a key outside the span the digits were planned for)
-        ctx->pred_counts_valid = false;                   // the synchronous path re-learns everything
-        ctx->order_cur = -1; ctx->order_pending = -1;
-        clear_stage_flags(ctx);
-        return FORMA_RETRY;
-    }
-    if (ctx->order_pending >= 0) {
-        ctx->order_cur = ctx->order_pending; ctx->order_sig = ctx->order_pending_sig; ctx->order_pending = -1;
-        // steer the threshold: the heavy section should hold the few percent of the tiles that make the launch's tail
-        const uint32_t nh = ctx->h_info->n_heavy, nt = std::max(ctx->order_tiles, 1u);
-        if (nh * 16u > nt) ctx->order_thr = std::min<uint32_t>(ctx->order_thr + ctx->order_thr / 4u, 1u << 24);        // > 6 %
-        else if (nh * 50u < nt) ctx->order_thr = std::max<uint32_t>(ctx->order_thr - ctx->order_thr / 5u, 1u << 12);     // < 2 %
-        // ... of a scene that HAS a tail: a tile is heavy from twice the average on (sampled: FrameInfo::cost_*)
-        if (ctx->h_info->cost_n) {
-            const uint64_t mean = ((uint64_t)ctx->h_info->cost_sum << 8) / ctx->h_info->cost_n;
-            ctx->order_thr = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(ctx->order_thr, 2 * mean), 1u << 24);
-            // a FLAT scene (the 8K triangle scene: 262 144 tiles of ~21 k clocks, none beyond twice that) has no tail to hide, and
-            // the bookkeeping of the order — a flag byte per tile, the empty heavy section — costs its painter 10 %: three such
-            // frames in a row switch the order off for the next 256
-            if (ctx->order_thr <= 2 * mean && nh * 100u < nt) { if (++ctx->order_flat >= 3) { ctx->order_off = 256; ctx->order_flat = 0; ctx->order_cur = -1; } }
-            else ctx->order_flat = 0;
-        }
-    }
-    ctx->pred_N = N; ctx->pred_J = J; ctx->pred_max_row = ctx->h_info->max_row_runs;
-    if (ctx->bias_banned) ctx->bias_banned--;
-    int rc;
-    // (a deferred frame's image left speculatively behind its kernels; tiles that k_paint_huge paints only now: the crop is
-    //  copied again)
-    const bool in_place = ctx->image_sent && !(ctx->h_info->error & 8u);
-    const bool was_split = ctx->split_sent;
-    if ((rc = settle_split(ctx))) return rc;               // (a split frame: its bands have landed — or land before the crop is copied again)
-    if ((rc = finish_paint(ctx))) return rc;
-    if ((rc = copy_image_out(ctx, dst, stride_bytes, timing, a, in_place))) return rc;
-    if (dst && !(was_split && in_place)) HIPCHECK(hipStreamSynchronize(ctx->stream));   // (split: the tail has run, the copy stream is drained)
-    rc = finish_frame(ctx, timings, true);
-    frame_done(ctx, rc, a);
-    return rc;
+// a verified frame's painters left their heaviest-first lists: they become the current set, and the threshold is steered
+void take_over_order(forma_hip_ctx* ctx) {
+    if (ctx->order_pending < 0) return;
+    ctx->order_cur = ctx->order_pending; ctx->order_sig = ctx->order_pending_sig; ctx->order_pending = -1;
+    // steer the threshold: the heavy section should hold the few percent of the tiles that make the launch's tail
+    const uint32_t nh = ctx->h_info->n_heavy, nt = std::max(ctx->order_tiles, 1u);
+    if (nh * 16u > nt) ctx->order_thr = std::min<uint32_t>(ctx->order_thr + ctx->order_thr / 4u, 1u << 24);        // > 6 %
+    else if (nh * 50u < nt) ctx->order_thr = std::max<uint32_t>(ctx->order_thr - ctx->order_thr / 5u, 1u << 12);     // < 2 %
+    // ... of a scene that HAS a tail: a tile is heavy from twice the average on (sampled: FrameInfo::cost_*)
+    if (!ctx->h_info->cost_n) return;
+    const uint64_t mean = ((uint64_t)ctx->h_info->cost_sum << 8) / ctx->h_info->cost_n;
+    ctx->order_thr = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(ctx->order_thr, 2 * mean), 1u << 24);
+    // a FLAT scene (the 8K triangle scene: 262 144 tiles of ~21 k clocks, none beyond twice that) has no tail to hide, and
+    // the bookkeeping of the order — a flag byte per tile, the empty heavy section — costs its painter 10 %: three such
+    // frames in a row switch the order off for the next 256
+    if (ctx->order_thr <= 2 * mean && nh * 100u < nt) { if (++ctx->order_flat >= 3) { ctx->order_off = 256; ctx->order_flat = 0; ctx->order_cur = -1; } }
+    else ctx->order_flat = 0;
 }
 
-// forma_hip_counters' frame counters live in the context the caller holds (a frame slot books on its owner)
-inline forma_counters_t& frame_counters(forma_hip_ctx* ctx) { return (ctx->owner ? ctx->owner : ctx)->cnt; }
+// The verdict on a read-back-free frame whose FrameInfo has arrived.  FORMA_OK: its predictions held and are taken over.
+// FORMA_RETRY: a prediction failed, nothing of the frame may be used (it is run again synchronously, which re-learns
+// everything).  own_counts: the stream is the context's own geometry — N is checked against the bound it was rasterized under
+// and taken over with the line count; the painters of such a frame may have left their order lists (order_enable is raised by
+// enqueue_own_kernels only) and a void frame drops them; its bands may be on their way to `dst`, which the re-run writes again.
+// A received stream's N is bounded by the exchange plan (exchange_overflow, verify_frame) and predicts nothing here.
+int judge_frame(forma_hip_ctx* ctx, const FrameRequest& r, bool own_counts) {
+    const FrameInfo& fi = *ctx->h_info;
+    const uint32_t N = fi.n_segments, J = fi.n_runs;
+    ctx->n_seg = N; ctx->last_runs = J;
+    if (own_counts) ctx->n_compact = fi.n_compact;
+    if (!fi.plan_bad && J <= r.bJ && (!own_counts || N <= r.bN)) {
+        if (own_counts) { take_over_order(ctx); ctx->pred_N = N; }
+        ctx->pred_J = J; ctx->pred_max_row = fi.max_row_runs;
+        if (ctx->bias_banned) ctx->bias_banned--;
+        return FORMA_OK;
+    }
+    if (own_counts) { const int src = settle_split(ctx); if (src) return src; }
+    if (ctx->small_tried && fi.plan_bad) ctx->small_banned = true;   // (one cause of plan_bad: a slice beyond the small variant)
+    if (ctx->covl_tried && fi.plan_bad) ctx->covl_banned = true;     // (another: a row beyond the COVL carry variant's LDS)
+    if (ctx->plan_biased && fi.plan_bad) ban_bias(ctx);              // (another: a key outside the span the digits were planned for)
+    ctx->pred_counts_valid = false;
+    if (own_counts) { ctx->order_cur = -1; ctx->order_pending = -1; }
+    clear_stage_flags(ctx);
+    return FORMA_RETRY;
+}
 
-// the synchronous frame (first frame of a scene, or a prediction failed): N, the key masks and J are read back
-int render_sync(forma_hip_ctx* ctx, const PaintArgs& a, uint8_t* dst, size_t stride_bytes, bool timing, forma_timings_t* timings) {
+int gsp_overflow(forma_hip_ctx* ctx) {
+    ctx->xoverflowed = true;                               // (state, not text: multi_render re-plans on it)
+    return fail(ctx, FORMA_E_CAPACITY, "exchange: a bucket exceeds the pair capacity (re-plan)");
+}
+
+// The second half of an enqueued frame: wait, judge, deliver.  The frame is verified BEFORE anything more lands in caller memory:
+// a mispredicted frame is never delivered (the bands of a split frame aside, which the re-run overwrites).
+int verify_frame(forma_hip_ctx* ctx, const FrameRequest& r, const Front& f) {
+    int rc;
+    if (f.received) {
+        HIPCHECK(hipStreamSynchronize(ctx->stream));
+        if (ctx->h_info->exchange_overflow) return gsp_overflow(ctx);
+    } else if ((rc = wait_frame_tail(ctx, r.timing()))) return rc;
+    if ((rc = judge_frame(ctx, r, !f.received))) return rc;
+    return deliver(ctx, r, true, !f.received);
+}
+
+// The synchronous frame.  A speculated sort plan that the read-back masks refute costs one more attempt (run_paint: FORMA_RETRY).
+// The frame establishes the predictions the next one is enqueued under (N only where it is the context's own count).
+int run_sync(forma_hip_ctx* ctx, const FrameRequest& r, const Front& f) {
     int rc;
     for (int attempt = 0; attempt < 2; attempt++) {
-        if ((rc = poison_frame_buffers(ctx))) return rc;
-        if ((rc = run_rasterize_frame(ctx, a.width, a.height, timing, /*speculate=*/attempt == 0))) return rc;
-        if ((rc = run_sort(ctx, ctx->seg_u.as<uint64_t>(), DevCount{nullptr, (uint32_t)ctx->n_seg}, timing))) return rc;
-        rc = run_paint(ctx, DevCount{nullptr, (uint32_t)ctx->n_seg}, a, timing);
+        if ((rc = f.produce(ctx, r, attempt == 0))) return rc;
+        rc = run_paint(ctx, DevCount{nullptr, (uint32_t)ctx->n_seg}, r.paint(), r.timing());
         if (rc == FORMA_RETRY) { clear_stage_flags(ctx); continue; }
-        if (rc) return rc;
-        if ((rc = read_info(ctx)) || (rc = finish_paint(ctx))) return rc;
-        if ((rc = copy_image_out(ctx, dst, stride_bytes, timing, a))) return rc;
-        if (dst) HIPCHECK(hipStreamSynchronize(ctx->stream));
-        rc = finish_frame(ctx, timings, true);
-        if (rc == FORMA_OK) { ctx->pred_N = (uint32_t)ctx->n_seg; ctx->pred_J = ctx->last_runs; ctx->pred_counts_valid = true; }
-        frame_done(ctx, rc, a);
-        return rc;
+        if (rc || (rc = deliver(ctx, r, false, false))) return rc;
+        if (!f.received) ctx->pred_N = (uint32_t)ctx->n_seg;
+        ctx->pred_J = ctx->last_runs; ctx->pred_counts_valid = true;
+        return FORMA_OK;
     }
     return fail(ctx, FORMA_E_INTERNAL, "sort plan did not converge");
 }
 
-// one whole frame on one slot, returning when `dst` (if any) is written
-int render_on(forma_hip_ctx* ctx, uint8_t* dst, const PaintArgs& a, size_t stride_bytes, forma_timings_t* timings) {
-    const bool timing = timings != nullptr;
-    clear_stage_flags(ctx);
-    if (a.width != ctx->pred_w || a.height != ctx->pred_h) { ctx->pred_counts_valid = false; ctx->pred_w = a.width; ctx->pred_h = a.height; }
-    if (ctx->pred_valid && ctx->pred_counts_valid && !ctx->no_async) {
-        uint32_t bN, bJ;
-        ctx->split_want = dst != nullptr && !timing;        // (a frame into caller memory: the painter may run in bands, run_paint)
-        ctx->split_n = 0;
-        int rc = enqueue_async_frame(ctx, a, timing, &bN, &bJ);
-        ctx->split_want = false;
-        if (rc) return rc;
-        if ((rc = send_split_bands(ctx, dst, stride_bytes, a))) { (void)settle_split(ctx); return rc; }
-        rc = complete_async_frame(ctx, a, dst, stride_bytes, timing, timings, bN, bJ);
-        if (rc != FORMA_RETRY) return rc;
-        frame_counters(ctx).frames_rerun++;
-    } else frame_counters(ctx).frames_learned++;
-    return render_sync(ctx, a, dst, stride_bytes, timing, timings);
+// an enqueued frame is finished: verified and delivered, or run again
+int settle_frame(forma_hip_ctx* ctx, const FrameRequest& r, const Front& f) {
+    int rc = verify_frame(ctx, r, f);
+    if (rc == FORMA_RETRY) { frame_counters(ctx, f).frames_rerun++; rc = run_sync(ctx, r, f); }
+    return rc;
+}
+// One frame on one context.  parked == nullptr: it is delivered when this returns.  Else a frame that could be enqueued stays in
+// flight (*parked; settle_frame on the same request finishes it); one that could not is delivered now all the same.
+int start_frame(forma_hip_ctx* ctx, FrameRequest& r, const Front& f, bool* parked) {
+    if (!may_enqueue(ctx)) { frame_counters(ctx, f).frames_learned++; return run_sync(ctx, r, f); }
+    const int rc = f.enqueue(ctx, r, parked);
+    return rc || parked ? rc : settle_frame(ctx, r, f);
 }
 
-// frames in flight: finish the frame a slot still owes (wait, verify, re-run synchronously if a prediction failed)
+// a frame of the context's own geometry on one slot
+int render_on(forma_hip_ctx* ctx, FrameRequest& r, bool* parked) {
+    clear_stage_flags(ctx);
+    if (r.width != ctx->pred_w || r.height != ctx->pred_h) { ctx->pred_counts_valid = false; ctx->pred_w = r.width; ctx->pred_h = r.height; }
+    return start_frame(ctx, r, OWN_GEOMETRY, parked);
+}
+
+// frames in flight: finish the frame a slot still owes
 int settle_slot(forma_hip_ctx* sl) {
     if (!sl->pending) return FORMA_OK;
     sl->pending = false;
     forma_hip_ctx* ctx = sl;
     HIPCHECK(hipSetDevice(sl->device));
-    const forma_hip_ctx::Deferred& d = sl->def;
-    PaintArgs a{d.width, d.height, d.channels, d.clear, d.has_crop ? &d.crop : nullptr, -1, d.target, d.target_pitch, d.fmt};
-    int rc = complete_async_frame(sl, a, d.dst, d.stride, false, nullptr, d.bN, d.bJ);
-    if (rc == FORMA_RETRY) { frame_counters(sl).frames_rerun++; rc = render_sync(sl, a, d.dst, d.stride, false, nullptr); }
-    return rc;
+    return settle_frame(sl, sl->parked, OWN_GEOMETRY);
 }
+inline void take_err(forma_hip_ctx* owner, const forma_hip_ctx* sl) { if (sl != owner) memcpy(owner->err, sl->err, sizeof owner->err); }
 
 }  // namespace
 
@@ -1859,7 +1916,7 @@ int fd_drain(forma_hip_ctx* ctx) {
     int first = FORMA_OK;
     for (forma_hip_ctx* sl : ctx->slots) {
         const int rc = settle_slot(sl);
-        if (rc && !first) { first = rc; if (sl != ctx) memcpy(ctx->err, sl->err, sizeof ctx->err); }
+        if (rc && !first) { first = rc; take_err(ctx, sl); }
     }
     return first;
 }
@@ -1880,13 +1937,13 @@ void share_scene(forma_hip_ctx* o) {
     }
 }
 void invalidate_counts(forma_hip_ctx* o) {                 // new geometry / band: every slot re-learns N and J synchronously
-    o->pred_counts_valid = false; o->xpred_valid = false; o->small_banned = false; o->covl_banned = false; o->bias_banned = 0; o->bias_ban_len = 0; o->pred_range.valid = false;
-    o->order_off = 0; o->order_flat = 0; o->order_cur = -1; o->cull_on = false; o->pred_slice_len = 0;
-    for (forma_hip_ctx* sl : o->slots) { sl->order_off = 0; sl->order_flat = 0; sl->order_cur = -1; sl->cull_on = false; sl->pred_slice_len = 0; }
-    // a fused frame's unsorted stream is rebuilt from the scene's CURRENT lines and band (restore_unsorted): gone with them
-    if (o->seg_u_fused) { o->seg_u_fused = false; o->have_unsorted = false; }
-    for (forma_hip_ctx* sl : o->slots) if (sl->seg_u_fused) { sl->seg_u_fused = false; sl->have_unsorted = false; }
-    for (forma_hip_ctx* sl : o->slots) { sl->pred_counts_valid = false; sl->xpred_valid = false; sl->small_banned = false; sl->covl_banned = false; sl->bias_banned = 0; sl->bias_ban_len = 0; sl->pred_range.valid = false; }
+    for (size_t i = 0; i < std::max<size_t>(o->slots.size(), 1); i++) {
+        forma_hip_ctx* c = o->slots.empty() ? o : o->slots[i];             // (the owner is slots[0] whenever there are slots)
+        c->pred_counts_valid = false; c->xpred_valid = false; c->small_banned = false; c->covl_banned = false; c->bias_banned = 0; c->bias_ban_len = 0; c->pred_range.valid = false;
+        c->order_off = 0; c->order_flat = 0; c->order_cur = -1; c->cull_on = false; c->pred_slice_len = 0;
+        // a fused frame's unsorted stream is rebuilt from the scene's CURRENT lines and band (restore_unsorted): gone with them
+        if (c->seg_u_fused) { c->seg_u_fused = false; c->have_unsorted = false; }
+    }
 }
 }  // namespace
 
@@ -1913,48 +1970,23 @@ static int render_impl(forma_hip_ctx* ctx, uint8_t* dst, uint32_t width, uint32_
     ctx->cnt.frames++;
     if (ctx->multi) return multi_render(ctx, dst, width, height, stride_bytes, channels, clear_color, crop_or_null, cache_id, timings);
     HIPCHECK(hipSetDevice(ctx->device));
-    PaintArgs a{width, height, channels, clear_color, crop_or_null, cache_id, dt.target, dt.pitch, dt.fmt};
+    FrameRequest r(dst, width, height, stride_bytes, channels, clear_color, crop_or_null, cache_id, timings);
+    r.target = dt.target; r.target_pitch = dt.pitch; r.fmt = dt.fmt;
     // Several frames in flight: a device-resident frame without a cache is ENQUEUED on the next slot and this call returns;
     // it is verified (and, if a prediction failed, re-run) when the slot is needed again or when any call needs its result.
     // Frames that write caller memory, use a buffer-layer cache (frame k + 1 reads what frame k left in it) or ask for
     // timings keep the synchronous contract of the reference: `dst` is fully written when the call returns — unless the
     // caller asked for the deferred form (forma_hip_render_enqueue): then the image also travels while later frames run.
-    if (ctx->slots.size() > 1 && (!dst || defer_dst) && cache_id < 0 && !timings) {
-        forma_hip_ctx* sl = ctx->slots[ctx->next_slot++ % ctx->slots.size()];
-        if ((rc = settle_slot(sl))) { if (sl != ctx) memcpy(ctx->err, sl->err, sizeof ctx->err); return rc; }
-        ctx->last = sl;
-        clear_stage_flags(sl);
-        if (width != sl->pred_w || height != sl->pred_h) { sl->pred_counts_valid = false; sl->pred_w = width; sl->pred_h = height; }
-        if (sl->pred_valid && sl->pred_counts_valid && !sl->no_async) {
-            forma_hip_ctx::Deferred& d = sl->def;
-            d.width = width; d.height = height; memcpy(d.channels, channels, 4); memcpy(d.clear, clear_color, 16);
-            d.has_crop = crop_or_null != nullptr; if (crop_or_null) d.crop = *crop_or_null;
-            d.dst = dst; d.stride = stride_bytes;
-            d.target = dt.target; d.target_pitch = dt.pitch; d.fmt = dt.fmt;
-            PaintArgs as{width, height, d.channels, d.clear, d.has_crop ? &d.crop : nullptr, -1, d.target, d.target_pitch, d.fmt};
-            if (dt.target && (rc = wait_for_caller(ctx, sl->stream, dt.wait))) return rc;
-            sl->frame_has_dst = dst != nullptr;                   // (sort_workgroups: such a frame's digit passes keep the whole chip)
-            rc = enqueue_async_frame(sl, as, false, &d.bN, &d.bJ);
-            sl->frame_has_dst = false;
-            if (rc == FORMA_OK) sl->pending = true;
-            if (rc == FORMA_OK && dst) {
-                // the image leaves speculatively, in one piece behind the frame's kernels (verified at settle time; a void frame
-                // is run again into `dst`): it crosses PCIe while the NEXT frames are rasterized, sorted and painted
-                rc = copy_image_out(sl, dst, stride_bytes, false, as);
-                sl->image_sent = rc == FORMA_OK;
-            }
-        } else {
-            if (dt.target && (rc = wait_for_caller(ctx, sl->stream, dt.wait))) return rc;
-            ctx->cnt.frames_learned++;
-            rc = render_sync(sl, a, dst, stride_bytes, false, nullptr);
-        }
-        if (rc && sl != ctx) memcpy(ctx->err, sl->err, sizeof ctx->err);
-        return rc;
-    }
-    if ((rc = fd_drain(ctx))) return rc;
-    ctx->last = ctx;
-    if (dt.target && (rc = wait_for_caller(ctx, ctx->stream, dt.wait))) return rc;
-    return render_on(ctx, dst, a, stride_bytes, timings);
+    const bool in_flight = ctx->slots.size() > 1 && (!dst || defer_dst) && cache_id < 0 && !timings;
+    forma_hip_ctx* sl = in_flight ? ctx->slots[ctx->next_slot++ % ctx->slots.size()] : ctx;
+    if (in_flight) { if ((rc = settle_slot(sl))) { take_err(ctx, sl); return rc; } }
+    else if ((rc = fd_drain(ctx))) return rc;
+    ctx->last = sl;
+    if (dt.target && (rc = wait_for_caller(ctx, sl->stream, dt.wait))) return rc;
+    if (in_flight) sl->parked = r;
+    rc = render_on(sl, in_flight ? sl->parked : r, in_flight ? &sl->pending : nullptr);
+    if (rc) take_err(ctx, sl);
+    return rc;
 }
 
 int forma_hip_render(forma_hip_ctx* ctx, uint8_t* dst, uint32_t width, uint32_t height, size_t stride_bytes,
@@ -2141,7 +2173,6 @@ int forma_hip_trim(forma_hip_ctx* ctx) {
         clear_stage_flags(c);
     }
     invalidate_counts(ctx);
-    ctx->pred_counts_valid = false; ctx->xpred_valid = false;
     return FORMA_OK;
 }
 
@@ -2316,12 +2347,9 @@ int forma_hip_sort_paint_frame(forma_hip_ctx* ctx, size_t n, uint8_t* dst, uint3
     ctx->live44 = 0xFFFFFFFFFFFull;                   // no varying-bit mask for a received stream: sort every digit
     ctx->layer_sorted = false; ctx->speculated = false; // slices that are layer-sorted need not concatenate to a layer-sorted stream
     if ((rc = run_sort(ctx, ctx->seg_u.as<uint64_t>(), DevCount{nullptr, (uint32_t)n}, timing))) return rc;
-    PaintArgs a{width, height, channels, clear_color, crop_or_null};
-    if ((rc = run_paint(ctx, DevCount{nullptr, (uint32_t)n}, a, timing))) return rc;
-    if ((rc = read_info(ctx)) || (rc = finish_paint(ctx))) return rc;
-    if ((rc = copy_image_out(ctx, dst, stride_bytes, timing, a))) return rc;
-    if (dst) HIPCHECK(hipStreamSynchronize(ctx->stream));
-    return finish_frame(ctx, timings, true);
+    const FrameRequest r(dst, width, height, stride_bytes, channels, clear_color, crop_or_null, -1, timings);
+    if ((rc = run_paint(ctx, DevCount{nullptr, (uint32_t)n}, r.paint(), timing))) return rc;
+    return deliver(ctx, r, false, false);
 }
 
 
@@ -2390,7 +2418,7 @@ int forma_hip_rasterize_bucket_frame(forma_hip_ctx* ctx, uint32_t width, uint32_
     // read-back-free on both halves: this call's first kernel also clears what the owner's half of the frame
     // (forma_hip_gather_sort_paint_frame: sort scratch, tile tables, run chain for a band of n_ranks x capacity segments) expects
     ZeroJobs Z; forma_hip_ctx::PreZero cleared;
-    const bool ahead = bN && ctx->pred_valid && ctx->pred_counts_valid && !ctx->no_async;
+    const bool ahead = bN && may_enqueue(ctx);
     if (ahead && (rc = plan_zero_jobs(ctx, width, height, ctx->xbands.n * ctx->xcap, ctx->xbands.n * ctx->xcap, &Z, &cleared))) return rc;
     if ((rc = run_rasterize_frame(ctx, width, height, timing, false, bN, ahead ? &Z : nullptr, ahead ? &cleared : nullptr))) return rc;
     FrameInfo* dinfo = ctx->info.as<FrameInfo>();
@@ -2428,35 +2456,19 @@ int forma_hip_gather_sort_paint_frame(forma_hip_ctx* ctx, uint8_t* dst, uint32_t
 
 }  // extern "C"
 
-// The owner's half of an exchange frame (forma_hip_gather_sort_paint_frame; a device of a multi-device context), in three
-// pieces so that a multi-device context can keep frames in flight: ENQUEUE (read-back-free: everything goes onto the stream,
-// nothing waits), COMPLETE (wait, verify the predictions, copy out) and the SYNCHRONOUS form (first frame of a plan, or a
-// prediction failed: N, the key masks and J are read back).
+// The owner's half of an exchange frame (forma_hip_gather_sort_paint_frame; a device of a multi-device context): the RECEIVED
+// front of the frame lifecycle (start_frame / settle_frame above), so that a multi-device context can keep frames in flight.
 namespace {
 
-struct GspArgs {
-    uint8_t* dst; uint32_t width, height; size_t stride_bytes; const uint8_t* channels; const float* clear; const forma_rect_t* crop;
-    int cache_id; forma_timings_t* timings;
-};
-
-int gsp_overflow(forma_hip_ctx* ctx) {
-    ctx->xoverflowed = true;                               // (state, not text: multi_render re-plans on it)
-    return fail(ctx, FORMA_E_CAPACITY, "exchange: a bucket exceeds the pair capacity (re-plan)");
-}
-
-// *enqueued = false: the context has no predictions yet (or read-back-free frames are off) — nothing was enqueued
-int gsp_enqueue(forma_hip_ctx* ctx, const GspArgs& g, bool* enqueued, uint32_t* bJ_out) {
-    *enqueued = false;
-    if (!(ctx->pred_valid && ctx->pred_counts_valid && !ctx->no_async)) return FORMA_OK;
-    const bool timing = g.timings != nullptr;
+// read-back-free: the key masks are speculated from the last verified frame, the stream's bound is the plan's (ranks x capacity)
+int enqueue_received(forma_hip_ctx* ctx, FrameRequest& r, bool* parked) {
+    const bool timing = r.timing();
     const uint32_t G = ctx->xbands.n, bound = G * ctx->xcap;
     const bool self = G == 1 && !ctx->xuse_recv;
     const uint64_t* recv = self ? ctx->xsend.as<uint64_t>() : ctx->xrecv.as<uint64_t>();
     FrameInfo* dinfo = ctx->info.as<FrameInfo>();
-    PaintArgs a{g.width, g.height, g.channels, g.clear, g.crop, g.cache_id};
     int rc;
-    const uint32_t bJ = ctx->pred_J + ctx->pred_J / 16 + 4096;
-    *bJ_out = bJ;
+    r.bJ = ctx->pred_J + ctx->pred_J / 16 + 4096;
     ctx->live44 = ctx->pred_live44; ctx->layer_sorted = ctx->pred_layer_sorted; ctx->speculated = true;
     uint64_t live = ctx->live44;
     if (ctx->layer_sorted) live &= ~0x1FFFFFull;
@@ -2478,76 +2490,36 @@ int gsp_enqueue(forma_hip_ctx* ctx, const GspArgs& g, bool* enqueued, uint32_t* 
         ctx->have_unsorted = true; ctx->n_lines = 0;
         if ((rc = run_sort(ctx, ctx->seg_u.as<uint64_t>(), DevCount{&dinfo->n_segments, bound}, timing))) return rc;
     }
-    if ((rc = run_paint(ctx, DevCount{&dinfo->n_segments, bound}, a, timing, bJ))) return rc;
+    if ((rc = run_paint(ctx, DevCount{&dinfo->n_segments, bound}, r.paint(), timing, r.bJ))) return rc;
     if ((rc = frame_tail(ctx, true, nullptr))) return rc;
-    *enqueued = true;
+    if (parked) *parked = true;
     return FORMA_OK;
 }
-
-// FORMA_RETRY: a prediction failed, nothing of the frame may be used (the caller runs gsp_sync)
-int gsp_complete(forma_hip_ctx* ctx, const GspArgs& g, uint32_t bJ) {
-    const bool timing = g.timings != nullptr;
-    PaintArgs a{g.width, g.height, g.channels, g.clear, g.crop, g.cache_id};
-    int rc;
-    HIPCHECK(hipStreamSynchronize(ctx->stream));
-    if (ctx->h_info->exchange_overflow) return gsp_overflow(ctx);
-    const uint32_t N = ctx->h_info->n_segments, J = ctx->h_info->n_runs;
-    ctx->n_seg = N; ctx->last_runs = J;
-    if (ctx->h_info->plan_bad && ctx->small_tried) ctx->small_banned = true;
-    if (ctx->h_info->plan_bad && ctx->covl_tried) ctx->covl_banned = true;
-    if (ctx->h_info->plan_bad && ctx->plan_biased) ban_bias(ctx);
-    if (!ctx->h_info->plan_bad && J <= bJ) {
-        if (ctx->bias_banned) ctx->bias_banned--;
-        ctx->pred_J = J; ctx->pred_max_row = ctx->h_info->max_row_runs;
-        if ((rc = finish_paint(ctx))) return rc;
-        if ((rc = copy_image_out(ctx, g.dst, g.stride_bytes, timing, a))) return rc;
-        if (g.dst) HIPCHECK(hipStreamSynchronize(ctx->stream));
-        rc = finish_frame(ctx, g.timings, true);
-        frame_done(ctx, rc, a);
-        return rc;
-    }
-    ctx->pred_counts_valid = false;
-    clear_stage_flags(ctx);
-    return FORMA_RETRY;
-}
-
-int gsp_sync(forma_hip_ctx* ctx, const GspArgs& g) {
-    const bool timing = g.timings != nullptr;
+// ... and synchronous (first frame of a plan, or a prediction failed): N, the key masks and J are read back
+int produce_received(forma_hip_ctx* ctx, const FrameRequest& r, bool) {
+    const bool timing = r.timing();
     const uint32_t G = ctx->xbands.n;
     const bool self = G == 1 && !ctx->xuse_recv;
     const uint64_t* recv = self ? ctx->xsend.as<uint64_t>() : ctx->xrecv.as<uint64_t>();
     FrameInfo* dinfo = ctx->info.as<FrameInfo>();
-    PaintArgs a{g.width, g.height, g.channels, g.clear, g.crop, g.cache_id};
     int rc;
-    ctx->pz = forma_hip_ctx::PreZero();
-    for (int attempt = 0; attempt < 2; attempt++) {                            // synchronous: N, key masks and J are read back
-        if ((rc = reset_info(ctx))) return rc;
-        stage_begin(ctx, ST_XCHG, timing);
-        launch_gather_chunks(ctx->stream, recv, G, ctx->xcap, ctx->seg_u.as<uint64_t>(), dinfo, ctx->xmask.as<uint32_t>(), /*reduce_now=*/true);
-        ctx->pending_masks = PendingMasks{nullptr, 0u};
-        stage_end(ctx, ST_XCHG, timing);
-        ctx->have_unsorted = true; ctx->n_lines = 0;
-        if ((rc = read_info(ctx))) return rc;
-        if (ctx->h_info->exchange_overflow) return gsp_overflow(ctx);
-        ctx->n_seg = ctx->h_info->n_segments;
-        const uint64_t k_or = (uint64_t)ctx->h_info->key_or | ((uint64_t)ctx->h_info->key_or_hi << 32);
-        const uint64_t k_and = (uint64_t)ctx->h_info->key_and | ((uint64_t)ctx->h_info->key_and_hi << 32);
-        ctx->live44 = ctx->n_seg ? ((k_or ^ k_and) & 0xFFFFFFFFFFFull) : 0;
-        ctx->layer_sorted = ctx->h_info->layer_unsorted == 0; ctx->speculated = false;
-        if ((rc = run_sort(ctx, ctx->seg_u.as<uint64_t>(), DevCount{nullptr, (uint32_t)ctx->n_seg}, timing))) return rc;
-        rc = run_paint(ctx, DevCount{nullptr, (uint32_t)ctx->n_seg}, a, timing);
-        if (rc == FORMA_RETRY) { clear_stage_flags(ctx); continue; }
-        if (rc) return rc;
-        if ((rc = read_info(ctx)) || (rc = finish_paint(ctx))) return rc;
-        if ((rc = copy_image_out(ctx, g.dst, g.stride_bytes, timing, a))) return rc;
-        if (g.dst) HIPCHECK(hipStreamSynchronize(ctx->stream));
-        rc = finish_frame(ctx, g.timings, true);
-        if (rc == FORMA_OK) { ctx->pred_J = ctx->last_runs; ctx->pred_counts_valid = true; }
-        frame_done(ctx, rc, a);
-        return rc;
-    }
-    return fail(ctx, FORMA_E_INTERNAL, "sort plan did not converge");
+    ctx->pz = forma_hip_ctx::PreZero();                    // (nothing was cleared ahead of its stage — and nothing on this path ever is)
+    if ((rc = reset_info(ctx))) return rc;
+    stage_begin(ctx, ST_XCHG, timing);
+    launch_gather_chunks(ctx->stream, recv, G, ctx->xcap, ctx->seg_u.as<uint64_t>(), dinfo, ctx->xmask.as<uint32_t>(), /*reduce_now=*/true);
+    ctx->pending_masks = PendingMasks{nullptr, 0u};
+    stage_end(ctx, ST_XCHG, timing);
+    ctx->have_unsorted = true; ctx->n_lines = 0;
+    if ((rc = read_info(ctx))) return rc;
+    if (ctx->h_info->exchange_overflow) return gsp_overflow(ctx);
+    ctx->n_seg = ctx->h_info->n_segments;
+    const uint64_t k_or = (uint64_t)ctx->h_info->key_or | ((uint64_t)ctx->h_info->key_or_hi << 32);
+    const uint64_t k_and = (uint64_t)ctx->h_info->key_and | ((uint64_t)ctx->h_info->key_and_hi << 32);
+    ctx->live44 = ctx->n_seg ? ((k_or ^ k_and) & 0xFFFFFFFFFFFull) : 0;
+    ctx->layer_sorted = ctx->h_info->layer_unsorted == 0; ctx->speculated = false;
+    return run_sort(ctx, ctx->seg_u.as<uint64_t>(), DevCount{nullptr, (uint32_t)ctx->n_seg}, timing);
 }
+constexpr Front RECEIVED{enqueue_received, produce_received, true};
 
 int gsp_prologue(forma_hip_ctx* ctx, uint8_t* dst, uint32_t width, uint32_t height, size_t stride_bytes, const uint8_t channels[4],
                  const float clear_color[4], int cache_id) {
@@ -2570,34 +2542,20 @@ int gsp_prologue(forma_hip_ctx* ctx, uint8_t* dst, uint32_t width, uint32_t heig
 int fd_gather_sort_paint(forma_hip_ctx* ctx, uint8_t* dst, uint32_t width, uint32_t height, size_t stride_bytes,
                          const uint8_t channels[4], const float clear_color[4], const forma_rect_t* crop_or_null, int cache_id,
                          forma_timings_t* timings) {
-    int rc = gsp_prologue(ctx, dst, width, height, stride_bytes, channels, clear_color, cache_id);
+    const int rc = gsp_prologue(ctx, dst, width, height, stride_bytes, channels, clear_color, cache_id);
     if (rc) return rc;
-    const GspArgs g{dst, width, height, stride_bytes, channels, clear_color, crop_or_null, cache_id, timings};
-    bool enqueued = false; uint32_t bJ = 0;
-    if ((rc = gsp_enqueue(ctx, g, &enqueued, &bJ))) return rc;
-    if (enqueued) {
-        rc = gsp_complete(ctx, g, bJ);
-        if (rc != FORMA_RETRY) return rc;
-        ctx->cnt.frames_rerun++;
-    } else ctx->cnt.frames_learned++;
-    return gsp_sync(ctx, g);
+    FrameRequest r(dst, width, height, stride_bytes, channels, clear_color, crop_or_null, cache_id, timings);
+    return start_frame(ctx, r, RECEIVED, nullptr);
 }
 
 // A device-resident, cache-less frame of a multi-device context with frames in flight: the owner's half is ENQUEUED (or, when
-// this slot has no predictions yet, run synchronously to its end) and the arguments are parked in the slot ...
+// this slot has no predictions yet, run synchronously to its end) and the request is parked in the slot ...
 int fd_gsp_defer(forma_hip_ctx* ctx, uint32_t width, uint32_t height, const uint8_t channels[4], const float clear_color[4],
                  const forma_rect_t* crop_or_null) {
-    int rc = gsp_prologue(ctx, nullptr, width, height, 0, channels, clear_color, -1);
+    const int rc = gsp_prologue(ctx, nullptr, width, height, 0, channels, clear_color, -1);
     if (rc) return rc;
-    forma_hip_ctx::Deferred& d = ctx->def;
-    d.width = width; d.height = height; memcpy(d.channels, channels, 4); memcpy(d.clear, clear_color, 16);
-    d.has_crop = crop_or_null != nullptr; if (crop_or_null) d.crop = *crop_or_null;
-    const GspArgs g{nullptr, width, height, 0, d.channels, d.clear, d.has_crop ? &d.crop : nullptr, -1, nullptr};
-    bool enqueued = false;
-    if ((rc = gsp_enqueue(ctx, g, &enqueued, &d.bJ))) return rc;
-    if (enqueued) { ctx->xpending = true; return FORMA_OK; }
-    ctx->cnt.frames_learned++;
-    return gsp_sync(ctx, g);
+    ctx->parked = FrameRequest(nullptr, width, height, 0, channels, clear_color, crop_or_null, -1, nullptr);
+    return start_frame(ctx, ctx->parked, RECEIVED, &ctx->xpending);
 }
 // ... and completed when the slot comes round again (or any call needs the result): FORMA_E_CAPACITY with ctx->xoverflowed when a
 // bucket outgrew the plan (the caller re-plans and re-runs the frame), any other failed prediction is repaired here
@@ -2605,11 +2563,7 @@ int fd_gsp_settle(forma_hip_ctx* ctx) {
     if (!ctx->xpending) return FORMA_OK;
     ctx->xpending = false;
     HIPCHECK(hipSetDevice(ctx->device));
-    const forma_hip_ctx::Deferred& d = ctx->def;
-    const GspArgs g{nullptr, d.width, d.height, 0, d.channels, d.clear, d.has_crop ? &d.crop : nullptr, -1, nullptr};
-    int rc = gsp_complete(ctx, g, d.bJ);
-    if (rc == FORMA_RETRY) { ctx->cnt.frames_rerun++; rc = gsp_sync(ctx, g); }
-    return rc;
+    return settle_frame(ctx, ctx->parked, RECEIVED);
 }
 
 

@@ -60,6 +60,43 @@ constexpr uint32_t PAINT_WAVES_PER_CU = 24;     // wave slots of the general pai
 constexpr size_t SEG_PAD = 16;          // segment buffers are over-allocated: stream kernels read whole 64-byte lane pieces
 enum { ST_PREPARE = 0, ST_RASTER, ST_SORT, ST_CARRY, ST_PAINT, ST_D2H, ST_XCHG, ST_COUNT };
 
+struct PaintArgs {
+    uint32_t width, height;
+    const uint8_t* channels;
+    const float* clear;
+    const forma_rect_t* crop;
+    int cache_id = -1;
+    // forma_hip_render_device: the painters write straight into the caller's device memory (pitch in bytes, FORMA_FORMAT_*);
+    // nullptr: into the context's scratch image or the cache's own image, as RGBA8
+    uint8_t* target = nullptr;
+    size_t target_pitch = 0;
+    uint32_t fmt = FORMA_FORMAT_SRGB8;
+    uint32_t tiles_w() const { return (width + 15) / 16; }  uint32_t tiles_h() const { return (height + 15) / 16; }
+};
+
+// One frame as its caller asked for it.  It OWNS its arguments (the caller's arrays need not outlive the call: a frame in flight
+// is parked in its slot, forma_hip_ctx::parked) and hands out the PaintArgs view of itself — valid while the request stays put.
+struct FrameRequest {
+    uint32_t width = 0, height = 0;
+    uint8_t channels[4] = {0, 1, 2, 3};
+    float clear[4] = {0, 0, 0, 0};
+    bool has_crop = false;
+    forma_rect_t crop = {0, 0, 0, 0};
+    int cache_id = -1;
+    uint8_t* target = nullptr; size_t target_pitch = 0; uint32_t fmt = FORMA_FORMAT_SRGB8;   // forma_hip_render_device: the caller's device target
+    uint8_t* dst = nullptr; size_t stride = 0;              // the frame also travels to caller memory
+    forma_timings_t* timings = nullptr;
+    uint32_t bN = 0, bJ = 0;                                // a read-back-free frame: the bounds its buffers were provisioned for
+    FrameRequest() = default;
+    FrameRequest(uint8_t* dst_, uint32_t w, uint32_t h, size_t stride_, const uint8_t ch[4], const float clear_[4], const forma_rect_t* crop_or_null,
+                 int cache, forma_timings_t* t) : width(w), height(h), has_crop(crop_or_null != nullptr), cache_id(cache), dst(dst_), stride(stride_), timings(t) {
+        memcpy(channels, ch, 4); memcpy(clear, clear_, 16);
+        if (crop_or_null) crop = *crop_or_null;
+    }
+    PaintArgs paint() const { return PaintArgs{width, height, channels, clear, has_crop ? &crop : nullptr, cache_id, target, target_pitch, fmt}; }
+    bool timing() const { return timings != nullptr; }
+};
+
 struct forma_hip_ctx {
     int device = 0;
     uint32_t n_cus = 256;                   // hipDeviceProp_t::multiProcessorCount of `device` (MI355X: 256)
@@ -154,7 +191,7 @@ struct forma_hip_ctx {
     static constexpr int SPLIT_MAX = 8;
     hipStream_t copy_stream = nullptr;      // created on first use
     hipEvent_t  split_ev[SPLIT_MAX] = {};
-    bool     split_want = false;            // set by render_on around the frame's enqueue: this frame may split
+    bool     split_want = false;            // set by enqueue_own around the frame's kernels: this frame may split
     int      split_n = 0;                   // bands of the frame just enqueued (0: not split)
     uint32_t split_row[SPLIT_MAX + 1] = {}; // tile-row boundaries of the bands
     bool     split_sent = false;            // copies are on copy_stream: wait for it before `dst` is touched again
@@ -212,15 +249,7 @@ struct forma_hip_ctx {
     unsigned next_slot = 0;
     forma_hip_ctx* last = nullptr;          // the slot that holds the most recent frame (inspection calls read it)
     bool pending = false;                   // this slot holds an enqueued frame nobody has verified yet
-    struct Deferred {
-        uint8_t* dst = nullptr; size_t stride = 0;           // forma_hip_render_enqueue: the frame also travels to caller memory
-        uint32_t width = 0, height = 0, bN = 0, bJ = 0;
-        uint8_t channels[4] = {0, 1, 2, 3};
-        float clear[4] = {0, 0, 0, 0};
-        bool has_crop = false;
-        forma_rect_t crop = {0, 0, 0, 0};
-        uint8_t* target = nullptr; size_t target_pitch = 0; uint32_t fmt = 0;   // forma_hip_render_device: the caller's device target
-    } def;
+    FrameRequest parked;                    // ... that frame (and the exchange frame of `xpending`)
     // several devices behind this context (forma_hip_create_multi): the context is then a shell, the work happens in
     // multi->kid[g] (one full context per device)
     struct MultiState* multi = nullptr;

@@ -146,7 +146,7 @@ def test_split_frames_into_a_padded_buffer_leave_the_rest_alone(monkeypatch, cas
 def test_a_split_frame_whose_prediction_fails_is_rendered_again(monkeypatch, split):
     """The bands of a split frame leave before the frame is verified (send_split_bands): when frame k + 1 has far more pixel
     segments than frame k predicted, the copies on their way are waited for, the frame runs again synchronously and `dst`
-    holds the right image when the call returns (complete_async_frame: settle_split before FORMA_RETRY)."""
+    holds the right image when the call returns (judge_frame: settle_split before FORMA_RETRY)."""
     import forma_amd
     monkeypatch.setenv("FORMA_HIP_DEBUG", split)
     rng = np.random.default_rng(5)

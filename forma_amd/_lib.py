@@ -80,7 +80,8 @@ class KeepRangeT(C.Structure):
 class CountersT(C.Structure):
     _fields_ = [("geometry_points", C.c_uint64), ("geometry_uploads", C.c_uint64), ("geometry_appends", C.c_uint64),
                 ("geometry_retains", C.c_uint64), ("geometry_bytes_h2d", C.c_uint64), ("geometry_bytes_d2h", C.c_uint64),
-                ("frames", C.c_uint64), ("frames_learned", C.c_uint64), ("frames_rerun", C.c_uint64)]
+                ("frames", C.c_uint64), ("frames_learned", C.c_uint64), ("frames_rerun", C.c_uint64),
+                ("table_edits", C.c_uint64), ("table_edit_bytes_h2d", C.c_uint64), ("scene_drains", C.c_uint64)]
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
@@ -96,6 +97,9 @@ SYMBOLS = {
     "forma_hip_version": (C.c_char_p, []),
     "forma_hip_set_geometry": (_i, [_vp, _vp, _vp, _vp, _sz]),
     "forma_hip_set_geoms": (_i, [_vp, _vp, _sz]),
+    "forma_hip_update_geoms": (_i, [_vp, _vp, _vp, _sz]),
+    "forma_hip_update_geoms_xf": (_i, [_vp, _u32, _u32, _vp]),
+    "forma_hip_read_geoms": (_i, [_vp, _vp, _sz, _vp]),
     "forma_hip_set_styles": (_i, [_vp, _vp, _sz, _vp, _sz, _vp]),
     "forma_hip_set_images": (_i, [_vp, _vp, _sz, _vp, _sz]),
     "forma_hip_flatten": (_i, [_vp, _vp, _vp, _vp]),

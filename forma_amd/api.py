@@ -387,6 +387,21 @@ class _Shared:
         self.pushes_epoch = 0          # bumped whenever `pushes` changes other than by an append at its end (compact_geom)
         self.table_version = 0         # bumped by every change that the per-frame layer / style tables depend on
         self.unchanged_version = 0     # bumped when a render call changes some layer's is_unchanged set
+        # changes through Layer.set_transform / set_is_enabled, kept apart from everything else the tables depend on: they touch
+        # one entry of the layer table each, and `Renderer(resident_tables=True)` sends just those.  xf_version counts them
+        # (each also bumps table_version); xf_log holds the layers of the changes xf_log_base .. xf_version, weakly
+        self.xf_version = 0
+        self.xf_log: list = []
+        self.xf_log_base = 0
+
+    def note_xf(self, layer: "Layer"):
+        self.table_version += 1
+        self.xf_version += 1
+        self.xf_log.append(weakref.ref(layer))
+        if len(self.xf_log) > 1 << 16:                    # (nobody reads that far back: a renderer that old takes the full path)
+            drop = len(self.xf_log) // 2
+            del self.xf_log[:drop]
+            self.xf_log_base += drop
 
     def new_geom_id(self) -> int:
         g = self.next_geom_id; self.next_geom_id += 1; return g
@@ -450,9 +465,11 @@ class Layer:
         return self.is_enabled_
 
     def set_is_enabled(self, v: bool) -> "Layer":
-        if self.is_enabled_ != v:
-            self._shared.table_version += 1
-        self.is_enabled_ = v; return self
+        changed = self.is_enabled_ != v
+        self.is_enabled_ = v
+        if changed:
+            self._shared.note_xf(self)
+        return self
 
     def disable(self):
         return self.set_is_enabled(False)
@@ -469,7 +486,7 @@ class Layer:
         if (old is None) != (new is None) or (old is not None and old.t != new.t):
             self.is_unchanged_.clear()
             self.affine_transform = new
-            self._shared.table_version += 1
+            self._shared.note_xf(self)
         return self
 
     def props(self) -> Props:
@@ -698,13 +715,16 @@ class BufferBuilder:
 class Renderer:
     """`forma::hip::Renderer`: same three methods as `cpu::Renderer` (cpu/renderer.rs:61-224)."""
 
-    def __init__(self, device: int = 0, devices=None, frames_in_flight: int = 1, resident_geometry: bool = False):
+    def __init__(self, device: int = 0, devices=None, frames_in_flight: int = 1, resident_geometry: bool = False,
+                 resident_tables: bool = False):
         """`Renderer::new()` (cpu/renderer.rs:63-65).  `devices`: one renderer over several GPUs of this process
         (forma_hip_create_multi — the Rust shim's `Renderer::with_devices`); `frames_in_flight`: device-resident frames
         are pipelined inside the renderer (forma_hip_set_frames_in_flight); `resident_geometry`: the setting for scenes
         whose geometry changes — the device's geometry store is appended to and compacted in place, at the cost of the
         edit, instead of being flattened and uploaded again as a whole (`host_tables` then holds no geometry: see
-        `read_geometry`)."""
+        `read_geometry`); `resident_tables`: the setting for scenes whose layers move — when nothing but transforms and
+        enabled flags changed since the last frame, only those entries of the layer table are sent (forma_hip_update_geoms /
+        _update_geoms_xf), and they travel with the frame instead of stopping the frames in flight."""
         self._ctx = Context(device, devices=devices, frames_in_flight=frames_in_flight)
         self._resident = bool(resident_geometry)
         self._dev_pushes: list = []                      # resident mode: the pushes on the device, in store order ...
@@ -718,6 +738,8 @@ class Renderer:
         self.host_tables: Dict[str, np.ndarray] = {}     # last uploaded scene tables (inspection / tests / bench)
         self._tables_key = None                          # (composition, table version, unchanged version, cache) on the device
         self._marked_key = None                          # (composition, table version, cache) whose layers are all marked unchanged
+        self._resident_tables = bool(resident_tables)
+        self._tables_mark = None                         # resident tables: (table version, xf version, slot map) the device tables were built at
 
     def create_buffer_layer_cache(self) -> Optional[BufferLayerCache]:     # at most 32 (SmallBitSet)
         for i in range(32):
@@ -920,9 +942,58 @@ class Renderer:
         # the layer / style / unchanged tables stay resident: they are rebuilt only when something they depend on changed
         key = (sh, sh.table_version, sh.unchanged_version if cache_id is not None else -1, cache_id)
         if key != self._tables_key:
-            self._upload_tables(composition, cache_id)
+            if not self._edit_tables(composition, cache_id):
+                self._upload_tables(composition, cache_id)
             self._tables_key = key
+            self._tables_mark = (sh.table_version, getattr(sh, "xf_version", 0), self._slot_of)
         return sh
+
+    def _edit_tables(self, comp: Composition, cache_id: Optional[int]) -> bool:
+        """resident tables: when only Layer.set_transform / set_is_enabled changed the composition since its tables were
+        uploaded (no cache involved, same slot map), build just those entries of the layer table and send them as one
+        update_geoms — or one update_geoms_xf when every slot got the same transform — and bring
+        host_tables["geoms"] up to date in place.  False: the caller takes the full path."""
+        if not getattr(self, "_resident_tables", False) or cache_id is not None:
+            return False
+        sh = comp._shared
+        mark, key = getattr(self, "_tables_mark", None), self._tables_key
+        if mark is None or key is None or key[0] is not sh or key[3] is not None or mark[2] is not self._slot_of:
+            return False
+        moved = sh.xf_version - mark[1]
+        if moved <= 0 or sh.table_version - mark[0] != moved or mark[1] < sh.xf_log_base:
+            return False
+        geoms = self.host_tables.get("geoms")
+        if geoms is None or len(geoms) != max(len(self._slot_of), 1):
+            return False
+        dirty: Dict[int, Layer] = {}
+        for ref in sh.xf_log[mark[1] - sh.xf_log_base:]:
+            layer = ref()
+            if layer is not None:
+                slot = self._slot_of.get(layer.geom_id_)
+                if slot is not None:
+                    dirty[slot] = layer
+        slots = np.array(sorted(dirty), np.uint32)
+        entries = np.zeros(len(slots), GEOM_DTYPE)
+        entries["order"] = NONE
+        for i, slot in enumerate(slots):
+            layer = dirty[int(slot)]
+            order = sh.geom_id_to_order.get(layer.geom_id_)
+            if order is None or not layer.is_enabled_ or comp.layers.get(layer.order) is not layer:
+                continue
+            entries[i]["order"] = order
+            if layer.affine_transform is not None:
+                entries[i]["flags"] = 1
+                entries[i]["xf"] = layer.affine_transform.t.to_array()
+        if len(slots):
+            xf_bits = np.ascontiguousarray(entries["xf"]).view(np.uint32)
+            one_xf = (len(slots) == len(geoms) and bool((entries["flags"] == 1).all())
+                      and bool((xf_bits == xf_bits[0]).all()) and np.array_equal(entries["order"], geoms["order"][slots]))
+            if one_xf:                                        # the demo's pan: 24 bytes, however many layers
+                self._ctx.update_geoms_xf(int(slots[0]), len(slots), entries["xf"][0])
+            else:
+                self._ctx.update_geoms(slots, entries)
+            geoms[slots] = entries
+        return True
 
     def _mark_unchanged(self, composition: Composition, sh, cache_id: Optional[int]):
         if cache_id is not None:                              # renderer.rs:217-223

@@ -106,6 +106,31 @@ class Context:
         g = np.ascontiguousarray(geoms, GEOM_DTYPE)
         self._check(self._L.forma_hip_set_geoms(self._h, _p(g), len(g)))
 
+    # ---- the layer table edited with frames in flight
+    def update_geoms(self, slots, entries):
+        """forma_hip_update_geoms: entries[i] (GEOM_DTYPE) replaces slot slots[i] of the layer table; the edit travels with the
+        next frame (no frame in flight is settled, nothing is waited for)"""
+        sl = np.ascontiguousarray(slots, np.uint32); g = np.ascontiguousarray(entries, GEOM_DTYPE)
+        assert len(sl) == len(g)
+        self._check(self._L.forma_hip_update_geoms(self._h, _p(sl), _p(g), len(sl)))
+
+    def update_geoms_xf(self, first, count, xf):
+        """forma_hip_update_geoms_xf: slots [first, first + count) get the transform xf (6 floats; None: identity, has_transform
+        cleared); their orders stay"""
+        m = None if xf is None else np.ascontiguousarray(xf, np.float32).reshape(6)
+        self._check(self._L.forma_hip_update_geoms_xf(self._h, int(first), int(count), _p(m)))
+
+    def read_geoms(self):
+        """forma_hip_read_geoms: the layer table the next frame will see (GEOM_DTYPE)"""
+        n = C.c_size_t(0)
+        rc = self._L.forma_hip_read_geoms(self._h, None, 0, C.byref(n))
+        if rc != 0 and rc != -4:
+            self._check(rc)
+        g = np.zeros(n.value, GEOM_DTYPE)
+        if n.value:
+            self._check(self._L.forma_hip_read_geoms(self._h, _p(g), n.value, C.byref(n)))
+        return g
+
     def set_styles(self, offsets, words, unchanged=None):
         o = np.ascontiguousarray(offsets, np.uint32); w = np.ascontiguousarray(words, np.uint32)
         u = None if unchanged is None else np.ascontiguousarray(unchanged, np.uint8)

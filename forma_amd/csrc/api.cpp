@@ -1125,6 +1125,180 @@ int upload(forma_hip_ctx* ctx, DevBuf& b, const T* src, size_t n) {
     return FORMA_OK;
 }
 
+// ---- layer-table edits that travel with the next frame (forma_hip_update_geoms / _update_geoms_xf) -----------------------------
+// The owner of the frame slots keeps the table on the host (h_tab) and a journal of which slots changed at which edit; every
+// frame slot owns a device table and, when its next frame starts, applies what it has not seen yet on its own stream — stream
+// order is the only ordering.  A slot has at most one frame in flight and is settled before its next one starts, so its
+// staging block is free again by then, and a frame that is voided and re-run finds the table it was enqueued with.
+inline forma_hip_ctx* tab_owner(forma_hip_ctx* c) { return c->owner ? c->owner : c; }
+inline std::vector<forma_hip_ctx*> tab_slots(forma_hip_ctx* o) { return o->slots.empty() ? std::vector<forma_hip_ctx*>{o} : o->slots; }
+
+// a scene call settles the frames in flight (counted when there were any)
+int scene_drain(forma_hip_ctx* ctx) {
+    for (const forma_hip_ctx* sl : ctx->slots) if (sl->pending) { ctx->cnt.scene_drains++; break; }
+    return fd_drain(ctx);
+}
+
+// every slot gets its table, its record buffer and its page-locked staging block, sized for the table as it is (a block of
+// records never exceeds the table: the whole table is copied instead); the journal's vectors get their final capacity
+int tables_provision(forma_hip_ctx* o) {
+    const size_t table_bytes = std::max<size_t>(o->n_geoms, 1) * sizeof(forma_geom_t), cap = std::max<size_t>(table_bytes, 1024);
+    for (forma_hip_ctx* ctx : tab_slots(o)) {
+        HIPCHECK(hipSetDevice(ctx->device));
+        const void* was = ctx->geoms_own.p;
+        HIPCHECK(ctx->geoms_own.ensure(table_bytes));
+        if (ctx->geoms_own.p != was) ctx->tab_seen = 0;               // a fresh table: the whole of it is due
+        if (ctx == o) {
+            // the owner's table moves too: the one the slots shared so far stays as it is (geoms_shared) — frames enqueued
+            // before the first edit call still read it — and `geoms` becomes a view of the owner's own table
+            if (!o->geoms.borrowed) { o->geoms_shared = o->geoms; o->geoms = DevBuf(); }
+            o->geoms.borrow(o->geoms_own);
+        }
+        HIPCHECK(ctx->tab_blob.ensure(cap));
+        if (ctx->h_tab_stage_cap < cap) {
+            const size_t want = std::max(cap, ctx->h_tab_stage_cap + ctx->h_tab_stage_cap / 2);
+            if (ctx->h_tab_stage) { (void)hipHostFree(ctx->h_tab_stage); ctx->h_tab_stage = nullptr; ctx->h_tab_stage_cap = 0; }
+            HIPCHECK(hipHostMalloc((void**)&ctx->h_tab_stage, want, hipHostMallocDefault));
+            ctx->h_tab_stage_cap = want;
+        }
+    }
+    o->tab_ent_seq.resize(o->n_geoms, 0);
+    o->tab_ent_log.reserve(2 * o->n_geoms + 96);         // (below n_geoms + 64 items before a call, which adds one per slot at most)
+    o->tab_rng_log.reserve(64);
+    return FORMA_OK;
+}
+
+// The first edit call: from here on every slot, the owner included, owns its table.  No frame is settled: the kernels of the
+// frames in flight keep reading the table the slots shared (geoms_shared), which nothing writes any more, and every slot's own
+// table is seeded from it with a device-to-device copy on the slot's stream — in front of a re-run of its frame and of its next
+// catch-up, and without touching the staging block (a copy out of that block behind a frame in flight would still be on its way
+// when the slot, whose frame's tail has been seen, packs its next records).  tab_on is raised once every slot is seeded.
+int tables_enable(forma_hip_ctx* o) {
+    forma_hip_ctx* ctx = o;
+    ctx->tab_ent_seq.assign(ctx->n_geoms, 0);
+    int rc = tables_provision(o);
+    if (rc) return rc;
+    const size_t table_bytes = o->n_geoms * sizeof(forma_geom_t);
+    if (!o->geoms_shared.p) return fail(o, FORMA_E_INTERNAL, "layer table: no shared table to seed the frame slots from");
+    for (forma_hip_ctx* sl : tab_slots(o)) {
+        ctx = sl;
+        HIPCHECK(hipSetDevice(sl->device));
+        HIPCHECK(hipMemcpyAsync(sl->geoms_own.p, o->geoms_shared.p, table_bytes, hipMemcpyDeviceToDevice, sl->stream));
+    }
+    ctx = o;
+    o->tab_on = true;
+    o->tab_seq = o->tab_full_seq = 1;
+    for (forma_hip_ctx* sl : tab_slots(o)) sl->tab_seen = 1;
+    HIPCHECK(hipSetDevice(o->device));
+    share_scene(o);
+    return FORMA_OK;
+}
+
+// an edit has been recorded: a journal that outgrew the table (a slot that renders no frames holds it back) collapses into
+// "copy the whole table"
+void tables_recorded(forma_hip_ctx* o) {
+    o->cnt.table_edits++;
+    if (o->tab_ent_log.size() >= o->n_geoms + 64 || o->tab_rng_log.size() >= 32) {
+        o->tab_ent_log.clear(); o->tab_rng_log.clear();
+        o->tab_full_seq = o->tab_seq;
+    }
+}
+
+// Bring this slot's table up to date, on its stream, in front of whatever reads the table next.
+int tables_catch_up(forma_hip_ctx* ctx) {
+    forma_hip_ctx* o = tab_owner(ctx);
+    if (!o->tab_on || ctx->tab_seen == o->tab_seq) return FORMA_OK;
+    HIPCHECK(hipSetDevice(ctx->device));
+    const uint32_t n = (uint32_t)o->n_geoms;
+    const size_t table_bytes = (size_t)n * sizeof(forma_geom_t);
+    const uint64_t seen = ctx->tab_seen;
+    if (n) {
+        bool full = seen < o->tab_full_seq;
+        size_t r0 = o->tab_rng_log.size(), e0 = o->tab_ent_log.size(), n_rng = 0, n_ent = 0;
+        if (!full) {
+            while (r0 > 0 && o->tab_rng_log[r0 - 1].seq > seen) r0--;
+            while (e0 > 0 && o->tab_ent_log[e0 - 1].seq > seen) e0--;
+            n_rng = o->tab_rng_log.size() - r0;
+            for (size_t i = e0; i < o->tab_ent_log.size(); i++) n_ent += o->tab_ent_seq[o->tab_ent_log[i].slot] == o->tab_ent_log[i].seq;
+            const size_t rec_bytes = (n_rng + n_ent) * sizeof(GeomEditRec);
+            full = n_rng > 8 || (rec_bytes > table_bytes && rec_bytes > 1024) || rec_bytes > ctx->h_tab_stage_cap || rec_bytes > ctx->tab_blob.cap;
+        }
+        if (full) {
+            if (table_bytes > ctx->h_tab_stage_cap || table_bytes > ctx->geoms.cap) return fail(ctx, FORMA_E_INTERNAL, "layer table: a frame slot was not provisioned");
+            memcpy(ctx->h_tab_stage, o->h_tab.data(), table_bytes);
+            HIPCHECK(hipMemcpyAsync(ctx->geoms.p, ctx->h_tab_stage, table_bytes, hipMemcpyHostToDevice, ctx->stream));
+            o->cnt.table_edit_bytes_h2d += table_bytes;
+        } else if (n_rng + n_ent) {
+            GeomEditRec* rec = reinterpret_cast<GeomEditRec*>(ctx->h_tab_stage);
+            size_t k = 0;
+            for (size_t i = r0; i < o->tab_rng_log.size(); i++, k++) {
+                const forma_hip_ctx::TabRng& r = o->tab_rng_log[i];
+                rec[k].kind = GE_RANGE; rec[k].first = r.first; rec[k].count = r.count; rec[k].pad = 0;
+                rec[k].entry.order = 0; rec[k].entry.flags = r.has_xf ? FORMA_GEOM_HAS_XF : 0u; memcpy(rec[k].entry.xf, r.xf, sizeof r.xf);
+            }
+            for (size_t i = e0; i < o->tab_ent_log.size(); i++) {
+                const forma_hip_ctx::TabEnt& e = o->tab_ent_log[i];
+                if (o->tab_ent_seq[e.slot] != e.seq) continue;               // (a later edit of the slot is in the block)
+                rec[k].kind = GE_ENTRY; rec[k].first = e.slot; rec[k].count = 1; rec[k].pad = 0; rec[k].entry = o->h_tab[e.slot];
+                k++;
+            }
+            const size_t rec_bytes = k * sizeof(GeomEditRec);
+            HIPCHECK(hipMemcpyAsync(ctx->tab_blob.p, rec, rec_bytes, hipMemcpyHostToDevice, ctx->stream));
+            o->cnt.table_edit_bytes_h2d += rec_bytes;
+            const GeomEditRec* dev = ctx->tab_blob.as<GeomEditRec>();
+            forma_geom_t* table = ctx->geoms.as<forma_geom_t>();
+            // ranges in call order: a launch takes the longest run of ranges that are pairwise disjoint.  The entries carry the
+            // table's CURRENT value (every range already folded in), so they go last: in the last launch of ranges when they
+            // touch none of its slots, else in a launch of their own
+            size_t g0 = 0;
+            auto longest = [&](size_t a, size_t b) { uint32_t m = 0; for (size_t j = a; j < b; j++) m = std::max(m, rec[j].count); return m; };
+            for (size_t i = 1; i < n_rng; i++) {
+                bool cut = false;
+                for (size_t j = g0; j < i && !cut; j++)
+                    cut = rec[j].first < rec[i].first + rec[i].count && rec[i].first < rec[j].first + rec[j].count;
+                if (!cut) continue;
+                launch_geom_edit(ctx->stream, dev + g0, (uint32_t)(i - g0), 0u, longest(g0, i), table, n);
+                g0 = i;
+            }
+            bool together = n_rng > g0 && n_ent > 0;
+            for (size_t e = n_rng; e < n_rng + n_ent && together; e++)
+                for (size_t j = g0; j < n_rng && together; j++)
+                    together = !(rec[e].first >= rec[j].first && rec[e].first - rec[j].first < rec[j].count);
+            if (together) launch_geom_edit(ctx->stream, dev + g0, (uint32_t)(n_rng - g0), (uint32_t)n_ent, longest(g0, n_rng), table, n);
+            else {
+                if (n_rng > g0) launch_geom_edit(ctx->stream, dev + g0, (uint32_t)(n_rng - g0), 0u, longest(g0, n_rng), table, n);
+                if (n_ent) launch_geom_edit(ctx->stream, dev + n_rng, 0u, (uint32_t)n_ent, 0u, table, n);
+            }
+            HIPCHECK(hipGetLastError());
+        }
+        // (the lines move with the transforms: a fused frame's unsorted stream cannot be rebuilt from this table — restore_unsorted)
+        if (ctx->seg_u_fused) { ctx->seg_u_fused = false; ctx->have_unsorted = false; }
+    }
+    ctx->tab_seen = o->tab_seq;
+    ctx->n_geoms = o->n_geoms; ctx->max_geom_order = o->tab_max_order;
+    // the journal is trimmed to the slot that has seen least
+    uint64_t oldest = o->tab_seq;
+    for (const forma_hip_ctx* sl : tab_slots(o)) oldest = std::min(oldest, sl->tab_seen);
+    size_t dr = 0, de = 0;
+    while (dr < o->tab_rng_log.size() && o->tab_rng_log[dr].seq <= oldest) dr++;
+    while (de < o->tab_ent_log.size() && o->tab_ent_log[de].seq <= oldest) de++;
+    if (dr) o->tab_rng_log.erase(o->tab_rng_log.begin(), o->tab_rng_log.begin() + (long)dr);
+    if (de) o->tab_ent_log.erase(o->tab_ent_log.begin(), o->tab_ent_log.begin() + (long)de);
+    return FORMA_OK;
+}
+
+// every slot up to date and its stream idle (multi-device contexts, whose frames do not start in render_on)
+int tables_sync_all(forma_hip_ctx* o) {
+    for (forma_hip_ctx* ctx : tab_slots(o)) {
+        HIPCHECK(hipSetDevice(ctx->device));
+        HIPCHECK(hipStreamSynchronize(ctx->stream));                  // (the staging block may still be on its way: the first edit call)
+        const int rc = tables_catch_up(ctx);
+        if (rc) return rc;
+        HIPCHECK(hipStreamSynchronize(ctx->stream));
+    }
+    return FORMA_OK;
+}
+
 }  // namespace
 
 // entry points that work on the context's own frame buffers: frames in flight are finished first; on a multi-device context
@@ -1132,13 +1306,13 @@ int upload(forma_hip_ctx* ctx, DevBuf& b, const T* src, size_t n) {
 #define ENTER_STAGE(ctx)                                                                        \
     do {                                                                                        \
         if (ctx->multi) ctx = multi_first(ctx);                                                 \
-        else { const int _rc = fd_drain(ctx); if (_rc) return _rc; ctx->last = ctx; }           \
+        else { int _rc = fd_drain(ctx); if (!_rc) _rc = tables_catch_up(ctx); if (_rc) return _rc; ctx->last = ctx; } \
     } while (0)
 #define ENTER_SINGLE(ctx)                                                                       \
     do {                                                                                        \
         if (!ctx) return FORMA_E_ARG;                                                           \
         if (ctx->multi) return fail(ctx, FORMA_E_STATE, "not available on a multi-device context (forma_hip_render does the whole frame)"); \
-        const int _rc = fd_drain(ctx); if (_rc) return _rc; ctx->last = ctx;                    \
+        int _rc = fd_drain(ctx); if (!_rc) _rc = tables_catch_up(ctx); if (_rc) return _rc; ctx->last = ctx; \
     } while (0)
 
 extern "C" {
@@ -1226,6 +1400,8 @@ void forma_hip_destroy(forma_hip_ctx* ctx) {
     if (ctx->h_written) (void)hipHostFree(ctx->h_written);
     if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
     if (ctx->h_geo) (void)hipHostFree(ctx->h_geo);
+    ctx->geoms_own.release(); ctx->geoms_shared.release(); ctx->tab_blob.release();
+    if (ctx->h_tab_stage) (void)hipHostFree(ctx->h_tab_stage);
     for (auto& c : ctx->caches) { c.tiles.release(); c.image.release(); }
     for (auto& r : ctx->registered) (void)hipHostUnregister(r.first);
     if (ctx->copy_stream) {
@@ -1249,7 +1425,7 @@ int forma_hip_set_geometry(forma_hip_ctx* ctx, const float* x, const float* y, c
     if (ctx->multi) return multi_set_geometry(ctx, x, y, line_slot, n_points);
     HIPCHECK(hipSetDevice(ctx->device));
     int rc;
-    if ((rc = fd_drain(ctx))) return rc;                  // frames in flight still read the old buffers
+    if ((rc = scene_drain(ctx))) return rc;               // frames in flight still read the old buffers
     if ((rc = upload(ctx, ctx->x, x, n_points))) return rc;
     if ((rc = upload(ctx, ctx->y, y, n_points))) return rc;
     HIPCHECK(ctx->line_slot.ensure(std::max<size_t>(n_points, 1) * 4));   // (n_points entries: the store's last point starts no line,
@@ -1274,15 +1450,89 @@ int forma_hip_set_geoms(forma_hip_ctx* ctx, const forma_geom_t* geoms, size_t n_
     }
     if (ctx->multi) return multi_set_geoms(ctx, geoms, n_geoms);
     HIPCHECK(hipSetDevice(ctx->device));
-    int rc = fd_drain(ctx);
+    int rc = scene_drain(ctx);
     if (rc) return rc;
-    if ((rc = upload(ctx, ctx->geoms, geoms, n_geoms))) return rc;
+    if ((rc = upload(ctx, ctx->geoms.borrowed ? ctx->geoms_own : ctx->geoms, geoms, n_geoms))) return rc;   // (edits in use: `geoms` is a view of geoms_own)
+    if (ctx->geoms.borrowed) ctx->geoms.borrow(ctx->geoms_own);
     HIPCHECK(hipStreamSynchronize(ctx->stream));
     ctx->n_geoms = n_geoms; ctx->max_geom_order = max_order;
+    // the table on the host (forma_hip_read_geoms, the edit calls); once edits are in use the other frame slots own tables, which
+    // take the whole of the new one when their next frame starts
+    ctx->h_tab.assign(geoms, geoms + n_geoms); ctx->tab_max_order = max_order;
+    if (ctx->tab_on) {
+        ctx->tab_seq++; ctx->tab_full_seq = ctx->tab_seq; ctx->tab_seen = ctx->tab_seq;
+        ctx->tab_ent_log.clear(); ctx->tab_rng_log.clear(); ctx->tab_ent_seq.assign(n_geoms, 0);
+        if ((rc = tables_provision(ctx))) return rc;
+        HIPCHECK(hipSetDevice(ctx->device));
+    }
     // (transforms move the lines: a fused frame's unsorted stream can no longer be rebuilt from them — restore_unsorted)
     if (ctx->seg_u_fused) { ctx->seg_u_fused = false; ctx->have_unsorted = false; }
     for (forma_hip_ctx* sl : ctx->slots) if (sl->seg_u_fused) { sl->seg_u_fused = false; sl->have_unsorted = false; }
     share_scene(ctx);
+    return FORMA_OK;
+}
+
+int forma_hip_update_geoms(forma_hip_ctx* ctx, const uint32_t* slots, const forma_geom_t* entries, size_t n) {
+    if (!ctx) return FORMA_E_ARG;
+    if (n == 0) return FORMA_OK;
+    if (!slots || !entries) return fail(ctx, FORMA_E_ARG, "null slots / entries");
+    if (ctx->multi) return multi_update_geoms(ctx, slots, entries, n);
+    for (size_t i = 0; i < n; i++) {
+        if (slots[i] >= ctx->n_geoms) return fail(ctx, FORMA_E_ARG, "slot beyond the layer table (forma_hip_set_geoms sizes it)");
+        if (entries[i].order != FORMA_NONE && entries[i].order > FORMA_LAYER_LIMIT) return fail(ctx, FORMA_E_ARG, "order exceeds LAYER_LIMIT");
+    }
+    if (!ctx->tab_on) { const int rc = tables_enable(ctx); if (rc) return rc; }
+    const uint64_t seq = ++ctx->tab_seq;
+    bool rescan = false;                                  // an entry that held the largest order got another one
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t sl = slots[i];
+        forma_geom_t& g = ctx->h_tab[sl];
+        if (g.order != FORMA_NONE && g.order == ctx->tab_max_order && entries[i].order != g.order) rescan = true;
+        g = entries[i];
+        if (g.order != FORMA_NONE) ctx->tab_max_order = std::max(ctx->tab_max_order, g.order);
+        if (ctx->tab_ent_seq[sl] != seq) { ctx->tab_ent_seq[sl] = seq; ctx->tab_ent_log.push_back({seq, sl}); }
+    }
+    if (rescan) {
+        uint32_t m = 0;
+        for (const forma_geom_t& g : ctx->h_tab) if (g.order != FORMA_NONE) m = std::max(m, g.order);
+        ctx->tab_max_order = m;
+    }
+    tables_recorded(ctx);
+    return FORMA_OK;
+}
+
+int forma_hip_update_geoms_xf(forma_hip_ctx* ctx, uint32_t first, uint32_t count, const float xf[6]) {
+    if (!ctx) return FORMA_E_ARG;
+    if (count == 0) return FORMA_OK;
+    if (ctx->multi) return multi_update_geoms_xf(ctx, first, count, xf);
+    if ((uint64_t)first + count > ctx->n_geoms) return fail(ctx, FORMA_E_ARG, "range beyond the layer table (forma_hip_set_geoms sizes it)");
+    if (!ctx->tab_on) { const int rc = tables_enable(ctx); if (rc) return rc; }
+    static const float identity[6] = {1.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f};
+    forma_hip_ctx::TabRng r{++ctx->tab_seq, first, count, xf ? 1u : 0u, {0, 0, 0, 0, 0, 0}};
+    memcpy(r.xf, xf ? xf : identity, sizeof r.xf);
+    for (uint32_t i = 0; i < count; i++) {
+        forma_geom_t& g = ctx->h_tab[first + i];
+        g.flags = (g.flags & ~FORMA_GEOM_HAS_XF) | (r.has_xf ? FORMA_GEOM_HAS_XF : 0u);
+        memcpy(g.xf, r.xf, sizeof r.xf);
+    }
+    // ranges stay ranges; one that this range covers has nothing left to say (the pan: one record however many frames are in flight)
+    std::vector<forma_hip_ctx::TabRng>& log = ctx->tab_rng_log;
+    log.erase(std::remove_if(log.begin(), log.end(), [&](const forma_hip_ctx::TabRng& a) {
+                  return a.first >= first && (uint64_t)a.first + a.count <= (uint64_t)first + count; }), log.end());
+    log.push_back(r);
+    tables_recorded(ctx);
+    return FORMA_OK;
+}
+
+int forma_hip_read_geoms(forma_hip_ctx* ctx, forma_geom_t* out, size_t capacity, size_t* out_n) {
+    if (!ctx || !out_n) return fail(ctx, FORMA_E_ARG, "null out_n");
+    if (ctx->multi) ctx = multi_first(ctx);
+    const size_t n = ctx->n_geoms;
+    *out_n = n;
+    if (n > capacity) return fail(ctx, FORMA_E_CAPACITY, "layer table capacity too small");
+    if (n == 0) return FORMA_OK;
+    if (!out) return fail(ctx, FORMA_E_ARG, "null layer table output");
+    memcpy(out, ctx->h_tab.data(), n * sizeof(forma_geom_t));
     return FORMA_OK;
 }
 
@@ -1327,7 +1577,7 @@ int forma_hip_set_styles(forma_hip_ctx* ctx, const uint32_t* style_offsets, size
     }
     HIPCHECK(hipSetDevice(ctx->device));
     int rc;
-    if ((rc = fd_drain(ctx))) return rc;
+    if ((rc = scene_drain(ctx))) return rc;
     if ((rc = upload(ctx, ctx->style_off, style_offsets, n_orders))) return rc;
     if ((rc = upload(ctx, ctx->style_words, style_words, n_words))) return rc;
     if ((rc = upload(ctx, ctx->layer_sf, ctx->h_layer_sf.data(), n_orders))) return rc;
@@ -1351,7 +1601,7 @@ int forma_hip_set_images(forma_hip_ctx* ctx, const forma_image_t* images, size_t
     if (ctx->multi) return multi_set_images(ctx, images, n_images, texels, n_texels);
     HIPCHECK(hipSetDevice(ctx->device));
     int rc;
-    if ((rc = fd_drain(ctx))) return rc;
+    if ((rc = scene_drain(ctx))) return rc;
     if ((rc = upload(ctx, ctx->images, images, n_images))) return rc;
     if ((rc = upload(ctx, ctx->texels, texels, n_texels * 4))) return rc;
     HIPCHECK(hipStreamSynchronize(ctx->stream));
@@ -1456,7 +1706,7 @@ int forma_hip_geometry_append(forma_hip_ctx* ctx, const forma_flatten_tables_t* 
     if (ctx->n_points + np >= (1ull << 30)) return fail(ctx, FORMA_E_ARG, "too many points");
     HIPCHECK(hipSetDevice(ctx->device));
     int rc;
-    if ((rc = fd_drain(ctx))) return rc;                  // frames in flight still read the store (and it may move when it grows)
+    if ((rc = scene_drain(ctx))) return rc;               // frames in flight still read the store (and it may move when it grows)
     // ONE packed block: 4 words per point (3 work items + the line slot), 16 per quad (3 x 3 control values + 7 scalars), 4 per
     // spline, 8 per affine range
     const size_t words = 4 * np + (9 + 7) * nq + 4 * ns + 8 * n_affines;
@@ -1509,7 +1759,7 @@ int forma_hip_geometry_retain(forma_hip_ctx* ctx, const forma_keep_range_t* keep
     if (ctx->multi) return multi_geometry_retain(ctx, keep, n_keep, slot_remap, n_slots);
     HIPCHECK(hipSetDevice(ctx->device));
     int rc;
-    if ((rc = fd_drain(ctx))) return rc;
+    if ((rc = scene_drain(ctx))) return rc;
     // the ranges: ascending, disjoint, inside the store; their destination offsets are the prefix sums of their lengths
     uint64_t end = 0, n_out = 0;
     size_t n_live = 0;
@@ -1894,6 +2144,7 @@ int start_frame(forma_hip_ctx* ctx, FrameRequest& r, const Front& f, bool* parke
 // a frame of the context's own geometry on one slot
 int render_on(forma_hip_ctx* ctx, FrameRequest& r, bool* parked) {
     clear_stage_flags(ctx);
+    { const int rc = tables_catch_up(ctx); if (rc) return rc; }        // layer-table edits travel with the frame, on its stream
     if (r.width != ctx->pred_w || r.height != ctx->pred_h) { ctx->pred_counts_valid = false; ctx->pred_w = r.width; ctx->pred_h = r.height; }
     return start_frame(ctx, r, OWN_GEOMETRY, parked);
 }
@@ -1929,8 +2180,10 @@ void share_scene(forma_hip_ctx* o) {
         if (sl == o) continue;
         const std::vector<DevBuf*> mine = sl->scene_bufs(), theirs = o->scene_bufs();
         for (size_t i = 0; i < mine.size(); i++) mine[i]->borrow(*theirs[i]);
+        if (o->tab_on && sl->geoms_own.p) sl->geoms.borrow(sl->geoms_own);   // (layer-table edits: the slot's own table)
         sl->n_points = o->n_points; sl->n_geoms = o->n_geoms; sl->n_orders = o->n_orders; sl->n_words = o->n_words; sl->n_images = o->n_images;
-        sl->max_geom_order = o->max_geom_order; sl->max_image_index = o->max_image_index; sl->any_texture = o->any_texture;
+        sl->max_geom_order = o->tab_on ? o->tab_max_order : o->max_geom_order;   // (edits in use: the table's, which the slot holds or takes before its next frame)
+        sl->max_image_index = o->max_image_index; sl->any_texture = o->any_texture;
         sl->scene_has_clips = o->scene_has_clips; sl->scene_simple = o->scene_simple; sl->costly_layers = o->costly_layers; sl->have_unchanged = o->have_unchanged;
         sl->band_row0 = o->band_row0; sl->band_row1 = o->band_row1;
         sl->line_ranged = o->line_ranged; sl->line_lo = o->line_lo; sl->line_hi = o->line_hi;
@@ -2083,6 +2336,7 @@ int forma_hip_set_frames_in_flight(forma_hip_ctx* ctx, int n) {
     }
     if (ctx->slots.size() == 1) ctx->slots.clear();
     ctx->next_slot = 0; ctx->last = ctx;
+    if (ctx->tab_on && (rc = tables_provision(ctx))) return rc;       // (new slots: their tables, due in whole)
     HIPCHECK(hipSetDevice(ctx->device));
     share_scene(ctx);
     return FORMA_OK;
@@ -2172,6 +2426,7 @@ int forma_hip_trim(forma_hip_ctx* ctx) {
         c->last_written = 0;
         clear_stage_flags(c);
     }
+    ctx->geoms_shared.release();                          // (every stream is idle: nothing reads the table the slots once shared)
     invalidate_counts(ctx);
     return FORMA_OK;
 }
@@ -2197,6 +2452,8 @@ int forma_hip_read_segments(forma_hip_ctx* ctx, int which, uint64_t* out, size_t
     ctx = last_slot(ctx);                                 // the slot that rendered the most recent frame
     if (ctx != owner) ctx->err[0] = 0;
     struct CopyErr { forma_hip_ctx* o; forma_hip_ctx* s; ~CopyErr() { if (o != s && s->err[0]) memcpy(o->err, s->err, sizeof o->err); } } copy_err{owner, ctx};
+    if (which == 0) { HIPCHECK(hipSetDevice(ctx->device)); const int rc = tables_catch_up(ctx); if (rc) return rc;
+                      HIPCHECK(hipStreamSynchronize(ctx->stream)); }   // (restore_unsorted reads the table; the staging block is free again)
     return fd_read_stream(ctx, which, out, capacity, out_n);
 }
 
@@ -2621,6 +2878,14 @@ int fd_row_histogram(forma_hip_ctx* ctx, uint32_t width, uint32_t height, uint32
 }
 
 forma_hip_ctx* fd_last_slot(forma_hip_ctx* ctx) { return ctx->last ? ctx->last : ctx; }
+int fd_update_geoms_now(forma_hip_ctx* ctx, const uint32_t* slots, const forma_geom_t* entries, size_t n) {
+    const int rc = forma_hip_update_geoms(ctx, slots, entries, n);
+    return rc ? rc : tables_sync_all(ctx);
+}
+int fd_update_geoms_xf_now(forma_hip_ctx* ctx, uint32_t first, uint32_t count, const float* xf) {
+    const int rc = forma_hip_update_geoms_xf(ctx, first, count, xf);
+    return rc ? rc : tables_sync_all(ctx);
+}
 
 int fd_copy_image_rows(forma_hip_ctx* ctx, uint8_t* dst, size_t stride_bytes, uint32_t y0, uint32_t y1) {
     if (!ctx || !dst) return FORMA_E_ARG;

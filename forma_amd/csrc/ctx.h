@@ -9,6 +9,7 @@
 
 #include "common.h"
 #include "debug.h"
+#include "geom_edit.h"
 
 struct DevBuf {
     void* p = nullptr;
@@ -115,6 +116,25 @@ struct forma_hip_ctx {
     DevBuf geo_flag;                        // k_geom_retain: a stored slot beyond the remap table
     uint8_t* h_geo = nullptr;               // pinned staging of geo_blob (grown geometrically, kept); its first word receives geo_flag
     size_t h_geo_cap = 0;
+    // the layer table edited with frames in flight (forma_hip_update_geoms / _update_geoms_xf; api.cpp "layer-table edits").
+    // The OWNER of the frame slots keeps the table on the host (h_tab: always, forma_hip_read_geoms answers from it) and, from
+    // the first edit call on (tab_on), a journal of what changed at which sequence number; every slot then owns a table
+    // (geoms_own; `geoms` is a view of it) and brings it up to date on its own stream when its next frame starts.
+    std::vector<forma_geom_t> h_tab;        // owner: the table the NEXT frame will see
+    bool tab_on = false;                    // owner: an edit call has been made — the slots own their tables
+    uint32_t tab_max_order = 0;             // owner: max_geom_order of h_tab (a slot takes it over with the table)
+    uint64_t tab_seq = 0, tab_full_seq = 0; // owner: number of the last edit / a slot that has seen less than tab_full_seq copies the whole table
+    std::vector<uint64_t> tab_ent_seq;      // owner, per table slot: the last edit that replaced the whole entry
+    struct TabEnt { uint64_t seq; uint32_t slot; };
+    struct TabRng { uint64_t seq; uint32_t first, count, has_xf; float xf[6]; };
+    std::vector<TabEnt> tab_ent_log;        // owner: entry edits, ascending seq (an item is stale when tab_ent_seq[slot] is newer)
+    std::vector<TabRng> tab_rng_log;        // owner: _xf ranges, ascending seq; a range that a later one covers is dropped
+    uint64_t tab_seen = 0;                  // every slot: the edit its table is up to date with
+    DevBuf geoms_own;                       // every slot, the owner included: its table
+    DevBuf geoms_shared;                    // owner: the table the slots shared before the first edit call (frames enqueued then still read it)
+    DevBuf tab_blob;                        // every slot: one catch-up's records on the device
+    uint8_t* h_tab_stage = nullptr;         // every slot, pinned: the records / the whole table on their way (free again once the slot's frame is settled)
+    size_t h_tab_stage_cap = 0;
     forma_counters_t cnt{};                 // forma_hip_counters (frame counters: kept by the owner of the frame slots)
     uint32_t max_geom_order = 0;            // largest order any geom slot names (FORMA_NONE slots aside)
     uint32_t max_image_index = 0;           // largest image index a texture style names
@@ -315,6 +335,10 @@ int fd_gsp_defer(forma_hip_ctx* ctx, uint32_t width, uint32_t height, const uint
 int fd_gsp_settle(forma_hip_ctx* ctx);
 // rows [y0, y1) of the context's last image -> dst (row-major, stride bytes per row, dst addresses row 0)
 int fd_copy_image_rows(forma_hip_ctx* ctx, uint8_t* dst, size_t stride_bytes, uint32_t y0, uint32_t y1);
+// layer-table edits on one device of a multi-device context: the edit, then EVERY frame slot's table brought up to date and
+// waited for (the caller has settled the frames)
+int fd_update_geoms_now(forma_hip_ctx* ctx, const uint32_t* slots, const forma_geom_t* entries, size_t n);
+int fd_update_geoms_xf_now(forma_hip_ctx* ctx, uint32_t first, uint32_t count, const float* xf);
 // the frame slot that holds the context's most recent frame (the context itself without frame slots)
 forma_hip_ctx* fd_last_slot(forma_hip_ctx* ctx);
 
@@ -332,6 +356,8 @@ int  multi_create(forma_hip_ctx** out, const int* devices, int n);
 void multi_destroy(forma_hip_ctx* ctx);
 int  multi_set_geometry(forma_hip_ctx* ctx, const float* x, const float* y, const uint32_t* line_slot, size_t n_points);
 int  multi_set_geoms(forma_hip_ctx* ctx, const forma_geom_t* geoms, size_t n_geoms);
+int  multi_update_geoms(forma_hip_ctx* ctx, const uint32_t* slots, const forma_geom_t* entries, size_t n);
+int  multi_update_geoms_xf(forma_hip_ctx* ctx, uint32_t first, uint32_t count, const float* xf);
 int  multi_geometry_append(forma_hip_ctx* ctx, const forma_flatten_tables_t* t, const uint32_t* line_slot,
                            const forma_affine_range_t* affines, size_t n_affines);
 int  multi_geometry_retain(forma_hip_ctx* ctx, const forma_keep_range_t* keep, size_t n_keep, const uint32_t* slot_remap, size_t n_slots);

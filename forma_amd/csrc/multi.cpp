@@ -783,6 +783,18 @@ int multi_set_geoms(forma_hip_ctx* ctx, const forma_geom_t* geoms, size_t n_geom
     EACH_KID(forma_hip_set_geoms(k, geoms, n_geoms));
     return FORMA_OK;
 }
+// edits of the layer table: frames are settled and every device applies the edit to all of its frame slots before the call
+// returns — correct, not fast (the devices hold the same table and refuse alike, the first one first)
+int multi_update_geoms(forma_hip_ctx* ctx, const uint32_t* slots, const forma_geom_t* entries, size_t n) {
+    MULTI_ENTER();
+    EACH_KID(fd_update_geoms_now(k, slots, entries, n));
+    return FORMA_OK;
+}
+int multi_update_geoms_xf(forma_hip_ctx* ctx, uint32_t first, uint32_t count, const float* xf) {
+    MULTI_ENTER();
+    EACH_KID(fd_update_geoms_xf_now(k, first, count, xf));
+    return FORMA_OK;
+}
 int multi_set_styles(forma_hip_ctx* ctx, const uint32_t* style_offsets, size_t n_orders, const uint32_t* style_words, size_t n_words,
                      const uint8_t* unchanged) {
     MULTI_ENTER();

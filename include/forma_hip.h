@@ -167,6 +167,37 @@ int forma_hip_set_styles(forma_hip_ctx* ctx, const uint32_t* style_offsets, size
 int forma_hip_set_images(forma_hip_ctx* ctx, const forma_image_t* images, size_t n_images,
                          const uint16_t* texels, size_t n_texels);
 
+/* ---- the layer table edited with frames in flight ------------------------------------------------ */
+/* forma_hip_set_geoms replaces the table, and like every scene upload it first settles the frames in flight and waits for
+ * the device.  These calls edit the table the NEXT frame will see and let the edit travel with that frame:
+ *   equivalence  after any sequence of set_geoms / update_geoms / update_geoms_xf every later frame renders what it would
+ *                after one forma_hip_set_geoms with the edited table; forma_hip_read_geoms returns that table bit for bit.
+ *   snapshot     a frame already enqueued renders the table as it was when it was enqueued, also when it is voided and
+ *                re-run later: from the first edit call on every frame slot owns its copy of the table (32 B per entry and
+ *                slot) and brings it up to date when its next frame starts, on its own stream — the pending records go out
+ *                as one block from a page-locked buffer of the slot and one kernel applies them; the whole table is copied
+ *                instead when that is less.
+ *   no stall     on a single-device context in steady state the calls settle no frame, do not wait for the device and
+ *                allocate nothing (the first edit call after create / set_frames_in_flight / a larger set_geoms provisions
+ *                the slots' tables and staging buffers; it settles no frame either).
+ *   batches      within one call a later record for the same slot wins; calls apply in call order, an _xf range that
+ *                overlaps earlier or later entry edits included.  n == 0 / count == 0: no-op.
+ *   errors       FORMA_E_ARG, and nothing changes: a slot or a range beyond the current n_geoms (only set_geoms resizes the
+ *                table), an order other than FORMA_NONE above FORMA_LAYER_LIMIT, a null pointer with n > 0.
+ *   state        as after set_geoms: a fused frame's unsorted stream is dropped once its slot has taken an edit, the
+ *                predictions of the read-back-free path stay (a frame that outgrows its bounds is voided and re-run).
+ * Every other reader of the table (the stage entry points, forma_hip_read_segments(0), the other scene calls) settles the
+ * frames as before and then sees the edited table.
+ * A multi-device context settles its frames and applies the edit on every device before the call returns: correct, not fast. */
+/* Replace n entries of the layer table: entries[i] takes slot slots[i]. */
+int forma_hip_update_geoms(forma_hip_ctx* ctx, const uint32_t* slots, const forma_geom_t* entries, size_t n);
+/* Give slots [first, first + count) one transform (xf == NULL: identity, FORMA_GEOM_HAS_XF cleared); `order` is left alone.
+ * This is the reference demo's pan (every layer gets the same transform each frame): 24 bytes per frame instead of the table. */
+int forma_hip_update_geoms_xf(forma_hip_ctx* ctx, uint32_t first, uint32_t count, const float xf[6]);
+/* Inspection: the table the NEXT frame will see.  *out_n = n_geoms; FORMA_E_CAPACITY (with *out_n set) if capacity is too
+ * small.  A multi-device context answers from its first device. */
+int forma_hip_read_geoms(forma_hip_ctx* ctx, forma_geom_t* out, size_t capacity, size_t* out_n);
+
 /* ---- stage 1: curve flattening (reference path.rs:473-538 `Primitives::into_segments`) ----- */
 /* Work items are produced by the host-side sequential pass (path.rs:252-445); all index
  * arrays are absolute into the quad / spline tables.  Appends nothing to the context: pure
@@ -231,6 +262,9 @@ typedef struct forma_counters_t {
     uint64_t frames;                                   /* frames rendered */
     uint64_t frames_learned;                           /* synchronous frames: no valid prediction of N, key masks, J */
     uint64_t frames_rerun;                             /* read-back-free frames voided on the device and rendered again */
+    uint64_t table_edits;                              /* forma_hip_update_geoms / _update_geoms_xf calls that changed the layer table */
+    uint64_t table_edit_bytes_h2d;                     /* what those edits sent to the device (records, or the whole table), all frame slots */
+    uint64_t scene_drains;                             /* scene calls that had to settle enqueued frames first */
 } forma_counters_t;
 int forma_hip_counters(forma_hip_ctx* ctx, forma_counters_t* out);
 

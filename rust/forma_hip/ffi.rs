@@ -174,6 +174,9 @@ pub struct forma_counters_t {
     pub frames: u64,
     pub frames_learned: u64,
     pub frames_rerun: u64,
+    pub table_edits: u64,
+    pub table_edit_bytes_h2d: u64,
+    pub scene_drains: u64,
 }
 
 /// `forma_kernel_time_t` (`include/forma_hip.h`): one kernel of the last timed frame, timed by its own launch events.
@@ -218,6 +221,20 @@ extern "C" {
         n_points: usize,
     ) -> c_int;
     pub fn forma_hip_set_geoms(ctx: *mut forma_hip_ctx, geoms: *const forma_geom_t, n_geoms: usize) -> c_int;
+    // the layer table edited with frames in flight: the edit travels with the next frame (no drain, no synchronise)
+    pub fn forma_hip_update_geoms(
+        ctx: *mut forma_hip_ctx,
+        slots: *const u32,
+        entries: *const forma_geom_t,
+        n: usize,
+    ) -> c_int;
+    pub fn forma_hip_update_geoms_xf(ctx: *mut forma_hip_ctx, first: u32, count: u32, xf: *const f32) -> c_int;
+    pub fn forma_hip_read_geoms(
+        ctx: *mut forma_hip_ctx,
+        out: *mut forma_geom_t,
+        capacity: usize,
+        out_n: *mut usize,
+    ) -> c_int;
     pub fn forma_hip_set_styles(
         ctx: *mut forma_hip_ctx,
         style_offsets: *const u32,

@@ -614,7 +614,18 @@ impl Renderer {
             unchanged[order.as_u32() as usize] = cache_id.map_or(false, |id| layer.is_unchanged(id)) as u8;
         }
 
-        if geoms != self.resident.geoms {
+        if geoms.len() == self.resident.geoms.len() && !geoms.is_empty() {
+            // Same slots, other entries (`Layer::set_transform` / `set_is_enabled`, `layer.rs:206-217`): only the entries that
+            // differ go out, and they travel with the next frame — no frame in flight is settled, nothing is waited for.
+            let slots: Vec<u32> = (0..geoms.len()).filter(|&i| geoms[i] != self.resident.geoms[i]).map(|i| i as u32).collect();
+            if !slots.is_empty() {
+                let entries: Vec<forma_geom_t> = slots.iter().map(|&slot| geoms[slot as usize]).collect();
+                // SAFETY: `slots` and `entries` hold `slots.len()` elements each; every slot is below the table's length.
+                let rc = unsafe { ffi::forma_hip_update_geoms(self.ctx, slots.as_ptr(), entries.as_ptr(), slots.len()) };
+                self.check(rc, "forma_hip_update_geoms");
+                self.resident.geoms = geoms;
+            }
+        } else if geoms != self.resident.geoms {
             // SAFETY: `geoms` holds `geoms.len()` entries.
             let rc = unsafe { ffi::forma_hip_set_geoms(self.ctx, geoms.as_ptr(), geoms.len()) };
             self.check(rc, "forma_hip_set_geoms");

@@ -177,7 +177,7 @@ int run_rasterize_frame(forma_hip_ctx* ctx, uint32_t width, uint32_t height, boo
         if (RH.hist && ctx->pz.slice_p && ctx->pz.slice_p == ctx->slice_buf.p && ctx->pz.slice_words >= slice_tab_words(bound_n) &&
             fuse_plan_ok(ctx, ctx->ras_plan)) {
             const SliceSrc SS = make_slice_src(ctx->slice_buf.as<uint32_t>(), bound_n);
-            RH.slice_tab = SS.tab; RH.tab_stride = SS.tab_stride;
+            RH.slice_tab = SS.tab; RH.tab_stride = SS.tab_stride; RH.rank_mode = (uint32_t)ctx->dbg.ras_rank;
             ctx->ras_fused = true;
         }
         // the tile fields' spans are worth measuring only where a biased plan could ever beat the plain one: the plain digits of

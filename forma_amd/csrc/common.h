@@ -235,7 +235,9 @@ struct RasHist { uint32_t* hist; uint32_t n_passes; uint32_t shift[RH_MAX_PASSES
                  uint32_t track_range; /* also measure what the keys' tile fields span (KeyRange for the next frame's plan): only
                                           where a field taken relative to its minimum can save a digit pass — else the records say "unknown" */
                  uint32_t* slice_tab; uint32_t tab_stride; /* != nullptr: the first digit pass is fused (SliceSrc) — each RAS_TILE block is
-                                          written partitioned by digit 0, its slices to slice_tab[d * tab_stride + b] */ };
+                                          written partitioned by digit 0, its slices to slice_tab[d * tab_stride + b] */
+                 uint32_t rank_mode; /* the fused partition's row rank (FORMA_HIP_DEBUG=ras_rank): 0 = 8-ballot match-any on every row,
+                                          1 = by runs of equal digit where that is exact, 2 = ... with the row test forced to fail */ };
 void launch_rasterize(hipStream_t s, const LineSource& src, DevCount n_compact, DevCount n_segments,
                       const uint32_t* cl_idx, const uint32_t* cl_start, const uint32_t* block_first, uint64_t* out,
                       FrameInfo* info, int band_row0, int band_row1, uint32_t* wg_masks /* 8 words per RAS_TILE block */,

@@ -19,6 +19,8 @@
 //   no_ras_hist          the sort's digit histograms are always taken by k_sort_hist, never by the rasterizer
 //   fuse_digit=0|1|2     read-back-free frames never / by policy (default) / always fuse the sort's first digit pass into the
 //                        rasterizer (SliceSrc; the policy: unless the last fused frame's slices averaged fewer than FUSE_MIN_SLICE keys)
+//   ras_rank=0|1|2       the fused partition ranks a row of 64 keys with the 8-ballot match-any always / by its runs of equal digit where
+//                        that is exact (default) / always, after making and failing the run test (the fallback's path on its own)
 //   carry_half=0|1|N     never / by policy / with N slices per row: the 512-lane carry kernel (three workgroups per CU)
 //   carry_covl=0|1       never / by policy (default): the carry kernel that stages a row's cover sums and style summaries in LDS
 //   paint_quad=0|1|2     the four-tiles-per-wavefront painter of all-solid scenes: never / by policy / always
@@ -50,7 +52,7 @@ struct ForMaDebug {
     bool sync = false, global_runsort = false, xgather = false, no_small_carry = false, span_groups = false, no_span_groups = false;
     bool no_packed_copy = false, no_simple_paint = false, force_simple_paint = false, trim_debug = false, force_exchange = false;
     bool xchg_copy = false, no_prezero = false, no_bias = false, no_ras_hist = false, no_cull = false, force_cull = false, no_order = false;
-    int carry_slices = 0, digit_bits = 0, poison = -1, poison_frame = -1, strip_tiles = -1, carry_half = 1, paint_quad = 1, order_thr = -1, sort_cus = -1, runs_chain = -1, multi_layout = 0, carry_covl = 1, runs_blk = -1, blk_round = 256, tail_poll = 1, paint_split = 1, split_first = 25, fuse_digit = 1;
+    int carry_slices = 0, digit_bits = 0, poison = -1, poison_frame = -1, strip_tiles = -1, carry_half = 1, paint_quad = 1, order_thr = -1, sort_cus = -1, runs_chain = -1, multi_layout = 0, carry_covl = 1, runs_blk = -1, blk_round = 256, tail_poll = 1, paint_split = 1, split_first = 25, fuse_digit = 1, ras_rank = 1;
 };
 
 inline ForMaDebug forma_debug_parse() {
@@ -83,6 +85,7 @@ inline ForMaDebug forma_debug_parse() {
         if (!strcmp(tok, "paint_split")) { d.paint_split = (int)std::min(std::max(v, 0L), 8L); continue; }
         if (!strcmp(tok, "split_first")) { d.split_first = (int)std::min(std::max(v, 1L), 99L); continue; }
         if (!strcmp(tok, "fuse_digit")) { d.fuse_digit = (int)std::min(std::max(v, 0L), 2L); continue; }
+        if (!strcmp(tok, "ras_rank")) { d.ras_rank = (int)std::min(std::max(v, 0L), 2L); continue; }
         if (!strcmp(tok, "tail_poll")) { d.tail_poll = (int)std::max(v, 0L); continue; }
         if (!strcmp(tok, "strip_tiles")) { d.strip_tiles = (int)std::max(v, 0L); continue; }
         if (!strcmp(tok, "poison")) { d.poison = (int)(v & 0xFF); continue; }

@@ -601,38 +601,123 @@ static_assert(sizeof(uint64_t) * RAS_TILE <= sizeof(RasWindow), "the partition s
 // consecutive keys, match-any, per-wave 16-bit counters in lh's first row, which the fused kernel does not count into), staged
 // in the dead line window, stored in 16-byte pieces.  Thread d < 256 then files the block's slice of digit d in the table and
 // counts it (digit 0's histogram and its blocks: what k_slice_scan needs for the logical positions).
+//
+// The rank of a row (the 64 keys w * PER_WAVE + j * 64 + lane, in stream order) by its RUNS of equal digit, where that is exact:
+// a row is 64 consecutive segments in raster order, so a few long runs are the rule (80 % of the 4K scene's rows pass the test
+// below).  A lane is a HEAD if it is lane 0 or its digit differs from lane - 1's (one DPP wave shift and a compare: H = the ballot
+// of the heads); its run starts at the highest bit of H at or below it, so its place in the run is a count of leading zeros under
+// a loop-invariant lane mask — no LDS, no ds_bpermute.  If every digit of the row owns ONE run (at most RAS_RUNS_MAX heads, their
+// digits read with v_readlane and compared pairwise on the scalar unit: wave-uniform and exact, never an approximation), the keys
+// of a digit are the lanes of its run: every lane reads its digit's counter, the run's LAST lane then adds the run's length (its
+// own place + 1), and rank = counter before the add + place in the run — the class leader's `counter after - length + lanes
+// below` of the 8-ballot form with the subtraction done by the order of the two LDS instructions, which a wave's LDS unit executes
+// in program order.  Every other row (more heads, or a digit that comes back: A,B,A) takes the 8-ballot form unchanged.  ~20 VALU
+// for ~44 — paid for with ~30 scalar instructions and three or four uniform branches per row, which is why 4 heads is the optimum:
+// 1 / 2 / 6 / 8 measured slower (NOTES.md).  (In k_onesweep, bound by HBM and its tile's serial life, the same idea lost: sort.hip.)
+// RH.rank_mode (FORMA_HIP_DEBUG=ras_rank): 0 = the 8-ballot form on every row, 1 = as above, 2 = the row test made and failed.
+#ifndef RAS_RUNS_MAX
+#define RAS_RUNS_MAX 4
+#endif
 __device__ __forceinline__ void ras_partition(const uint64_t (&vout)[RAS_PER_THREAD], uint64_t* __restrict__ out, const RasHist& RH,
                                               uint64_t* stg, uint16_t* wc /* [waves][256], cleared */, uint32_t* wsum /* [waves] */,
                                               uint32_t k0, uint32_t k1) {
     constexpr int WAVES = RAS_THREADS / 64, PER_WAVE = 64 * RAS_PER_THREAD;
     static_assert(WAVES * 256 * 2 <= SORT_BINS * 4, "the wave counters live in lh's first row");
     static_assert(RAS_THREADS == 256, "one digit per thread");
+    static_assert(RAS_PER_THREAD == 8, "eight 8-bit digits in two registers");
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const uint32_t sh = RH.shift[0], mk = RH.mask[0], bs = RH.bias[0];
+    const uint32_t sh = RH.shift[0], mk = RH.mask[0], bs = RH.bias[0], mode = RH.rank_mode;
     const uint32_t nloc = k1 - k0;
+    const bool full = nloc == RAS_TILE;                                 // (uniform: only the stream's last block can be short)
 #pragma unroll
     for (int q = 0; q < RAS_PER_THREAD; q += 2)
         *reinterpret_cast<ulonglong2*>(&stg[tid * RAS_PER_THREAD + q]) = make_ulonglong2(vout[q], vout[q + 1]);
-    __syncthreads();
+    // (no barrier: a wave's rows are the 512 keys its own lanes just staged, and a wave's LDS instructions execute in order;
+    //  the line window has been dead since the barriers of the mask reduction)
     uint64_t kk[RAS_PER_THREAD];
     uint32_t rk[RAS_PER_THREAD / 2];                                    // 16-bit ranks, two per register
+    uint32_t dg[RAS_PER_THREAD], dgp[RAS_PER_THREAD / 4];               // the keys' digits; four per register across the barriers
     uint32_t* wcw = reinterpret_cast<uint32_t*>(wc) + w * 128;
 #pragma unroll
-    for (int j = 0; j < RAS_PER_THREAD; j++) {
-        const uint32_t i = w * PER_WAVE + j * 64 + lane;
-        kk[j] = stg[i];
+    for (int j = 0; j < RAS_PER_THREAD; j++) kk[j] = stg[w * PER_WAVE + j * 64 + lane];
+    // the digits, once per key.  A full block by a uniform branch: no padding select; a digit in the key's high word (every
+    // digit of a layer-sorted frame) by another: one 32-bit shift instead of a 64-bit one (as the HIST loop does it)
+    if (full) {
+        if (sh >= 32) {
+            const uint32_t s = sh - 32;
+#pragma unroll
+            for (int j = 0; j < RAS_PER_THREAD; j++) dg[j] = (((uint32_t)(kk[j] >> 32) >> s) - bs) & mk;
+        } else {
+#pragma unroll
+            for (int j = 0; j < RAS_PER_THREAD; j++) dg[j] = ((uint32_t)(kk[j] >> sh) - bs) & mk;
+        }
+    } else {
         // padding (the last block's positions >= nloc): the LAST digit, so that it ranks behind every key of the block; it is
         // taken off that digit's count below and never stored
-        const uint32_t dg = i < nloc ? (((uint32_t)(kk[j] >> sh) - bs) & mk) : mk;
-        uint32_t mlo, mhi;
-        match_any<8>(dg, mlo, mhi);
-        const uint32_t below = lanes_below(mlo, mhi), cnt = (uint32_t)__popc(mlo) + (uint32_t)__popc(mhi);
-        const uint32_t hs = (dg & 1u) * 16u;
-        if (below == 0) atomicAdd(&wcw[dg >> 1], cnt << hs);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");    // compiler barrier: keep the read after the add
-        const uint32_t r = ((wcw[dg >> 1] >> hs) & 0xFFFFu) - cnt + below;
+#pragma unroll
+        for (int j = 0; j < RAS_PER_THREAD; j++)
+            dg[j] = (uint32_t)(w * PER_WAVE + j * 64 + lane) < nloc ? (((uint32_t)(kk[j] >> sh) - bs) & mk) : mk;
+    }
+    dgp[0] = dg[0] | (dg[1] << 8) | (dg[2] << 16) | (dg[3] << 24);
+    dgp[1] = dg[4] | (dg[5] << 8) | (dg[6] << 16) | (dg[7] << 24);
+    const uint64_t le = ~0ull >> (63 - lane);                           // lanes at or below mine
+    const uint32_t le_lo = (uint32_t)le, le_hi = (uint32_t)(le >> 32);
+#ifdef RAS_PROF
+    uint32_t rp_fast = 0;
+#endif
+#pragma unroll
+    for (int j = 0; j < RAS_PER_THREAD; j++) {
+        const uint32_t d = dg[j];
+        const uint32_t hs = (d & 1u) * 16u;
+        uint64_t H = 0;
+        bool fast = false;
+        if (mode) {                                                     // (uniform, like everything that decides `fast`)
+            // lane - 1's digit: wave_shr:1 (lane 0 has no source: it is a head anyway)
+            const uint32_t prev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)d, 0x138, 0xF, 0xF, true);
+            H = __ballot(prev != d) | 1ull;
+            const uint32_t nh = (uint32_t)__popc((uint32_t)H) + (uint32_t)__popc((uint32_t)(H >> 32));
+            fast = nh <= RAS_RUNS_MAX && mode == 1;
+            if (fast && nh > 1) {                                       // the heads' digits, pairwise different?
+                uint32_t hd[RAS_RUNS_MAX];
+                uint64_t h = H;
+#pragma unroll
+                for (int k = 0; k < RAS_RUNS_MAX; k++) {
+                    if ((uint32_t)k < nh) {
+                        hd[k] = (uint32_t)__builtin_amdgcn_readlane((int)d, (int)__builtin_ctzll(h));
+                        h &= h - 1;
+#pragma unroll
+                        for (int a = 0; a < k; a++) fast = fast && hd[a] != hd[k];
+                    }
+                }
+            }
+        }
+        uint32_t r;
+        if (fast) {
+            // lane + 1's digit: wave_shl:1 (lane 63 has no source: it is the last lane of its run anyway)
+            const uint32_t next = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)d, 0x130, 0xF, 0xF, true);
+            const uint32_t m_lo = (uint32_t)H & le_lo, m_hi = (uint32_t)(H >> 32) & le_hi;      // (bit 0 of H is always set)
+            const uint32_t pos = (uint32_t)lane - 63u + (uint32_t)__builtin_clzll(((uint64_t)m_hi << 32) | m_lo);
+            r = ((wcw[d >> 1] >> hs) & 0xFFFFu) + pos;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");    // compiler barrier: keep the add after the read
+            if (next != d || lane == 63) atomicAdd(&wcw[d >> 1], (pos + 1u) << hs);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");    // ... and the next row's read after the add
+#ifdef RAS_PROF
+            rp_fast++;
+#endif
+        } else {
+            uint32_t mlo, mhi;
+            match_any<8>(d, mlo, mhi);
+            const uint32_t below = lanes_below(mlo, mhi), cnt = (uint32_t)__popc(mlo) + (uint32_t)__popc(mhi);
+            if (below == 0) atomicAdd(&wcw[d >> 1], cnt << hs);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");    // compiler barrier: keep the read after the add
+            r = ((wcw[d >> 1] >> hs) & 0xFFFFu) - cnt + below;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        }
         if (j & 1) rk[j >> 1] |= r << 16; else rk[j >> 1] = r;
     }
+#ifdef RAS_PROF
+    if (lane == 0) { atomicAdd(&g_ras_prof[blockIdx.x & 63][5], (unsigned long long)rp_fast); atomicAdd(&g_ras_prof[blockIdx.x & 63][6], (unsigned long long)RAS_PER_THREAD); }
+#endif
     __syncthreads();
     {
         const uint32_t d = (uint32_t)tid;                           // (RAS_THREADS == 256: one digit per thread)
@@ -640,8 +725,13 @@ __device__ __forceinline__ void ras_partition(const uint64_t (&vout)[RAS_PER_THR
 #pragma unroll
         for (int q = 0; q < WAVES; q++) { c[q] = wc[q * 256 + d]; tot += c[q]; }
         uint32_t incl = tot;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const uint32_t v = __shfl_up(incl, o, 64); if (lane >= o) incl += v; }
+        // inclusive scan along the wave in six DPP adds (four row shifts, the two row broadcasts): no LDS round trips
+        incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x111, 0xF, 0xF, false);    // row_shr:1
+        incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x112, 0xF, 0xF, false);    // row_shr:2
+        incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x114, 0xF, 0xF, false);    // row_shr:4
+        incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x118, 0xF, 0xF, false);    // row_shr:8
+        incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x142, 0xA, 0xF, false);    // row_bcast:15 into rows 1, 3
+        incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x143, 0xC, 0xF, false);    // row_bcast:31 into rows 2, 3
         if (lane == 63) wsum[w] = incl;
         __syncthreads();
         uint32_t off = incl - tot;
@@ -660,16 +750,23 @@ __device__ __forceinline__ void ras_partition(const uint64_t (&vout)[RAS_PER_THR
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < RAS_PER_THREAD; j++) {
-        const uint32_t i = w * PER_WAVE + j * 64 + lane;
-        const uint32_t dg = i < nloc ? (((uint32_t)(kk[j] >> sh) - bs) & mk) : mk;
-        stg[wc[w * 256 + dg] + ((rk[j >> 1] >> ((j & 1) * 16)) & 0xFFFFu)] = kk[j];
+        const uint32_t d = (dgp[j >> 2] >> ((j & 3) * 8)) & 0xFFu;
+        stg[wc[w * 256 + d] + ((rk[j >> 1] >> ((j & 1) * 16)) & 0xFFFFu)] = kk[j];
     }
     __syncthreads();
+    if (full) {                                                     // 16-byte pieces, consecutive across the lanes
 #pragma unroll
-    for (int q = 0; q < RAS_PER_THREAD; q += 2) {
-        const uint32_t i = (uint32_t)q * RAS_THREADS + 2u * tid;   // 16-byte pieces, consecutive across the lanes
-        if (i + 1 < nloc) *reinterpret_cast<ulonglong2*>(out + k0 + i) = *reinterpret_cast<const ulonglong2*>(&stg[i]);
-        else if (i < nloc) out[k0 + i] = stg[i];
+        for (int q = 0; q < RAS_PER_THREAD; q += 2) {
+            const uint32_t i = (uint32_t)q * RAS_THREADS + 2u * tid;
+            *reinterpret_cast<ulonglong2*>(out + k0 + i) = *reinterpret_cast<const ulonglong2*>(&stg[i]);
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < RAS_PER_THREAD; q += 2) {
+            const uint32_t i = (uint32_t)q * RAS_THREADS + 2u * tid;
+            if (i + 1 < nloc) *reinterpret_cast<ulonglong2*>(out + k0 + i) = *reinterpret_cast<const ulonglong2*>(&stg[i]);
+            else if (i < nloc) out[k0 + i] = stg[i];
+        }
     }
 }
 

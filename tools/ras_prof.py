@@ -1,4 +1,5 @@
-"""Phase breakdown of k_rasterize (needs a -DRAS_PROF build: tools/build_variants.sh rprof:"-DRAS_PROF", copied over libforma_hip.so)."""
+"""Phase breakdown of k_rasterize, and the share of the fused partition's rows ranked by their runs (needs a -DRAS_PROF build:
+tools/build_variants.sh rprof:"-DRAS_PROF", copied over libforma_hip.so or named by FORMA_HIP_LIB)."""
 import ctypes as C, sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -24,3 +25,5 @@ print(f"{wl}: {wg / N:.0f} workgroups per frame")
 for i, n in enumerate(names):
     print(f"  {n:48s} {buf[i] / wg:8.0f} clocks/workgroup  {100 * buf[i] / tot:5.1f}%")
 print(f"  total {tot / wg:.0f} clocks per workgroup (thread 0)")
+if buf[6]:                                               # the fused partition: rows of 64 keys ranked by their runs (ras_partition)
+    print(f"  fused partition: {buf[5]} of {buf[6]} rows on the run-ranked path = {100 * buf[5] / buf[6]:.1f}%")

@@ -108,15 +108,15 @@ int run_line_table(forma_hip_ctx* ctx, const LineSource& src, size_t n_lines, bo
 LineSource geometry_source(forma_hip_ctx* ctx, uint32_t width, uint32_t height) {
     LineSource S;
     memset(&S, 0, sizeof S);
-    const size_t l0 = ctx->line_ranged ? ctx->line_lo : 0;              // a share of the lines: line i joins points i and i + 1
+    const size_t l0 = ctx->scene.line_ranged ? ctx->scene.line_lo : 0;              // a share of the lines: line i joins points i and i + 1
     S.x = ctx->x.as<float>() + l0; S.y = ctx->y.as<float>() + l0; S.line_slot = ctx->line_slot.as<uint32_t>() + l0;
-    S.geoms = ctx->geoms.as<forma_geom_t>(); S.n_geoms = (uint32_t)ctx->n_geoms;
+    S.geoms = ctx->geoms.as<forma_geom_t>(); S.n_geoms = (uint32_t)ctx->scene.n_geoms;
     S.width = (float)width; S.height = (float)height;
     S.band_lo = -3.0e38f; S.band_hi = 3.0e38f;
     // (an eighth of a pixel = two sub-pixel steps wider than the band: a line within half a sub-pixel step of the band's edge can
     //  round INTO the band's first or last tile row (a zero-cover segment: invisible, but part of the sorted stream) — lines are
     //  only culled where no rounding can bring them back; k_rasterize's exact tile-row test flags what a kept line leaves outside)
-    if (ctx->band_row1 > 0) { S.band_lo = (float)(ctx->band_row0 * 16u) - 0.125f; S.band_hi = (float)(ctx->band_row1 * 16u) + 0.125f; }
+    if (ctx->scene.band_row1 > 0) { S.band_lo = (float)(ctx->scene.band_row0 * 16u) - 0.125f; S.band_hi = (float)(ctx->scene.band_row1 * 16u) + 0.125f; }
     return S;
 }
 
@@ -139,8 +139,8 @@ static bool fuse_plan_ok(const forma_hip_ctx* ctx, const SortPlan& plan);
 int run_rasterize_frame(forma_hip_ctx* ctx, uint32_t width, uint32_t height, bool timing, bool speculate = false,
                         uint32_t bound_n = 0, const ZeroJobs* zero = nullptr, const forma_hip_ctx::PreZero* cleared = nullptr,
                         bool hist_too = false /* count the speculated sort plan's digits while the keys are made (RasHist) */) {
-    const size_t all_lines = ctx->n_points ? ctx->n_points - 1 : 0;
-    const size_t n_lines = ctx->line_ranged ? std::min(ctx->line_hi, all_lines) - std::min(ctx->line_lo, all_lines) : all_lines;
+    const size_t all_lines = ctx->scene.n_points ? ctx->scene.n_points - 1 : 0;
+    const size_t n_lines = ctx->scene.line_ranged ? std::min(ctx->scene.line_hi, all_lines) - std::min(ctx->scene.line_lo, all_lines) : all_lines;
     ctx->n_lines = n_lines;
     ctx->n_seg = 0; ctx->n_compact = 0; ctx->have_unsorted = true; ctx->live44 = 0; ctx->layer_sorted = true;
     ctx->speculated = false; ctx->ras_hist_on = false; ctx->ras_fused = false;
@@ -169,8 +169,8 @@ int run_rasterize_frame(forma_hip_ctx* ctx, uint32_t width, uint32_t height, boo
     // the plan the sort will use if the speculation holds (run_sort checks that it is the same plan)
     RasHist RH;
     memset(&RH, 0, sizeof RH);
-    if (hist_too && bound_n && ctx->pred_valid && ctx->pz.sort_p && ctx->pz.sort_p == ctx->sort_counters.p && !ctx->dbg.no_ras_hist) {
-        ctx->ras_plan = frame_sort_plan(ctx, ctx->pred_live44, ctx->pred_layer_sorted, ctx->digit_bits, true, nullptr);
+    if (hist_too && bound_n && ctx->learned.pred_valid && ctx->pz.sort_p && ctx->pz.sort_p == ctx->sort_counters.p && !ctx->dbg.no_ras_hist) {
+        ctx->ras_plan = frame_sort_plan(ctx, ctx->learned.pred_live44, ctx->learned.pred_layer_sorted, ctx->digit_bits(), true, nullptr);
         RH = make_ras_hist(ctx->ras_plan, ctx->sort_counters.as<uint32_t>());
         ctx->ras_hist_on = RH.hist != nullptr;
         // ... and the first digit pass with them, where the frame's first kernel cleared the slice table for this bound
@@ -184,25 +184,25 @@ int run_rasterize_frame(forma_hip_ctx* ctx, uint32_t width, uint32_t height, boo
         // the tile fields take more than two passes (canvases beyond 255 tiles in a dimension), or this frame's plan is biased
         // already (its digits are checked against the spans).  4K and below: no — 80 VALU instructions per rasterizer lane less.
         {
-            const SortPlan plain = make_segment_sort_plan(ctx->pred_live44, ctx->pred_layer_sorted, ctx->digit_bits, nullptr, nullptr);
-            const SortPlan lay = ctx->pred_layer_sorted ? SortPlan{} : make_sort_plan((ctx->pred_live44 & 0x1FFFFFull) << 20, 20, 41, ctx->digit_bits);
+            const SortPlan plain = make_segment_sort_plan(ctx->learned.pred_live44, ctx->learned.pred_layer_sorted, ctx->digit_bits(), nullptr, nullptr);
+            const SortPlan lay = ctx->learned.pred_layer_sorted ? SortPlan{} : make_sort_plan((ctx->learned.pred_live44 & 0x1FFFFFull) << 20, 20, 41, ctx->digit_bits());
             bool biased = false;
             for (int p = 0; p < ctx->ras_plan.n_passes; p++) biased |= ctx->ras_plan.fmask[p] != 0u;
-            RH.track_range = (biased || plain.n_passes > (ctx->pred_layer_sorted ? 0 : lay.n_passes) + 2) ? 1u : 0u;
+            RH.track_range = (biased || plain.n_passes > (ctx->learned.pred_layer_sorted ? 0 : lay.n_passes) + 2) ? 1u : 0u;
         }
     }
     stage_begin(ctx, ST_RASTER, timing);
     launch_rasterize(ctx->stream, S, nc_cmp, nc_seg, ctx->cl_idx.as<uint32_t>(), ctx->cl_start.as<uint32_t>(),
-                     ctx->block_first.as<uint32_t>(), ctx->seg_u.as<uint64_t>(), dinfo, (int)ctx->band_row0,
-                     (int)ctx->band_row1, ctx->ras_masks.as<uint32_t>(), /*reduce_now=*/bound_n == 0, &RH);
+                     ctx->block_first.as<uint32_t>(), ctx->seg_u.as<uint64_t>(), dinfo, (int)ctx->scene.band_row0,
+                     (int)ctx->scene.band_row1, ctx->ras_masks.as<uint32_t>(), /*reduce_now=*/bound_n == 0, &RH);
     // read-back-free frame: the masks stay per-workgroup records until k_runs_count combines them (nothing reads them earlier)
     ctx->pending_masks = bound_n ? PendingMasks{ctx->ras_masks.as<uint32_t>(), 0u, ctx->ras_hist_on ? 1u : 0u} : PendingMasks{nullptr, 0u, 0u};
     ctx->seg_u_fused = ctx->ras_fused; ctx->fused_w = width; ctx->fused_h = height;
     stage_end(ctx, ST_RASTER, timing);
     HIPCHECK(hipGetLastError());
-    ctx->speculated = (speculate || bound_n) && ctx->pred_valid;
+    ctx->speculated = (speculate || bound_n) && ctx->learned.pred_valid;
     if (ctx->speculated) {
-        ctx->live44 = ctx->pred_live44; ctx->layer_sorted = ctx->pred_layer_sorted;
+        ctx->live44 = ctx->learned.pred_live44; ctx->layer_sorted = ctx->learned.pred_layer_sorted;
         // (asynchronous frames: k_runs_count verifies the plan on the device before anything relies on the sort order)
         return FORMA_OK;
     }
@@ -248,7 +248,7 @@ static bool one_frame_in_flight(const forma_hip_ctx* ctx) {
 }
 static bool paint_by_strips(const forma_hip_ctx* ctx, uint32_t tiles_painted) {
     if (ctx->dbg.strip_tiles >= 0) return tiles_painted <= (uint32_t)ctx->dbg.strip_tiles;
-    return tiles_painted <= paint_strip_tiles(ctx) && !ctx->scene_simple && (uint64_t)ctx->costly_layers * 32u >= ctx->n_orders && one_frame_in_flight(ctx);
+    return tiles_painted <= paint_strip_tiles(ctx) && !ctx->scene.scene_simple && (uint64_t)ctx->scene.costly_layers * 32u >= ctx->scene.n_orders && one_frame_in_flight(ctx);
 }
 
 // Quad painters (k_paint_quad: four tiles per wavefront) for all-solid scenes whose tiles are shallow AND many: the list work of
@@ -257,7 +257,7 @@ static bool paint_by_strips(const forma_hip_ctx* ctx, uint32_t tiles_painted) {
 // pipelined), a loss where it is one or two (a 64-row band of that scene: 56 -> 72 us; 1080p: 23 -> 40 us).  Shallow = few runs
 // per tile (a tile with more than 16 entries after culling goes to k_paint_deep).  FORMA_HIP_DEBUG=paint_quad=0|2: never / always.
 static bool paint_by_quads(const forma_hip_ctx* ctx, int cache_id, uint32_t runs_bound, uint32_t tiles) {
-    if (!ctx->scene_simple || ctx->dbg.no_simple_paint || cache_id >= 0 || ctx->dbg.paint_quad == 0) return false;
+    if (!ctx->scene.scene_simple || ctx->dbg.no_simple_paint || cache_id >= 0 || ctx->dbg.paint_quad == 0) return false;
     if (ctx->dbg.paint_quad == 2) return true;
     return tiles >= 16u * 8192u && (uint64_t)runs_bound <= 8ull * tiles;     // (>= 4 rounds of quads on the chip's 8 192 wave slots)
 }
@@ -266,8 +266,8 @@ static bool paint_by_quads(const forma_hip_ctx* ctx, int cache_id, uint32_t runs
 // bound), so this is a suspicion, not a proof: plain digits for a while, then the cheaper plan is tried again; every repeat
 // doubles the ban (64 .. 4096 frames), new geometry lifts it (invalidate_counts).
 static void ban_bias(forma_hip_ctx* ctx) {
-    ctx->bias_ban_len = ctx->bias_ban_len ? std::min(ctx->bias_ban_len * 2u, 4096u) : 64u;
-    ctx->bias_banned = ctx->bias_ban_len;
+    ctx->learned.bias_ban_len = ctx->learned.bias_ban_len ? std::min(ctx->learned.bias_ban_len * 2u, 4096u) : 64u;
+    ctx->learned.bias_banned = ctx->learned.bias_ban_len;
 }
 
 // the digit plan of a frame's segment sort: live key bits only; a stream that is already non-decreasing in layer needs a
@@ -275,7 +275,7 @@ static void ban_bias(forma_hip_ctx* ctx) {
 SortPlan frame_sort_plan(forma_hip_ctx* ctx, uint64_t live44, bool layer_sorted, int digit_bits, bool speculated, bool* biased) {
     // the tile fields relative to their minima (one digit fewer on 4096- and 8192-pixel canvases): only on read-back-free
     // frames — the span is the PREVIOUS frame's, k_sort_hist checks this frame's keys against it and voids the frame otherwise
-    const KeyRange* range = speculated && ctx->pred_range.valid && !ctx->bias_banned && !ctx->dbg.no_bias ? &ctx->pred_range : nullptr;
+    const KeyRange* range = speculated && ctx->learned.pred_range.valid && !ctx->learned.bias_banned && !ctx->dbg.no_bias ? &ctx->learned.pred_range : nullptr;
     return make_segment_sort_plan(live44, layer_sorted, digit_bits, range, biased);
 }
 
@@ -297,16 +297,16 @@ SortPlan frame_sort_plan(forma_hip_ctx* ctx, uint64_t live44, bool layer_sorted,
 #define FUSE_PROBE 256
 #endif
 static bool fuse_plan_ok(const forma_hip_ctx* ctx, const SortPlan& plan) {
-    if (ctx->dbg.fuse_digit == 0 || ctx->dbg.no_ras_hist || ctx->digit_bits == 4) return false;
-    if (ctx->band_row1 > 0 || ctx->line_ranged) return false;
+    if (ctx->dbg.fuse_digit == 0 || ctx->dbg.no_ras_hist || ctx->digit_bits() == 4) return false;
+    if (ctx->scene.band_row1 > 0 || ctx->scene.line_ranged) return false;
     return plan.n_passes >= 2 && plan.n_passes <= RH_MAX_PASSES && plan.mask[0] <= 255u;
 }
 // decided once per frame, by plan_zero_jobs (the slice table is cleared only for a frame that fuses)
 static bool fuse_first_digit(forma_hip_ctx* ctx, const SortPlan& plan) {
     if (!fuse_plan_ok(ctx, plan)) return false;
-    if (ctx->dbg.fuse_digit == 2 || ctx->pred_slice_len == 0 || ctx->pred_slice_len >= FUSE_MIN_SLICE) return true;
-    if (++ctx->fuse_skipped < FUSE_PROBE) return false;
-    ctx->fuse_skipped = 0;
+    if (ctx->dbg.fuse_digit == 2 || ctx->learned.pred_slice_len == 0 || ctx->learned.pred_slice_len >= FUSE_MIN_SLICE) return true;
+    if (++ctx->learned.fuse_skipped < FUSE_PROBE) return false;
+    ctx->learned.fuse_skipped = 0;
     return true;
 }
 
@@ -321,7 +321,7 @@ int plan_zero_jobs(forma_hip_ctx* ctx, uint32_t width, uint32_t height, uint32_t
     *cleared = forma_hip_ctx::PreZero();
     if (ctx->dbg.no_prezero) return FORMA_OK;
     const uint32_t tiles_w = (width + 15) / 16, tiles_h = (height + 15) / 16;
-    const SortPlan plan = frame_sort_plan(ctx, ctx->pred_live44, ctx->pred_layer_sorted, ctx->digit_bits, true, nullptr);
+    const SortPlan plan = frame_sort_plan(ctx, ctx->learned.pred_live44, ctx->learned.pred_layer_sorted, ctx->digit_bits(), true, nullptr);
     HIPCHECK(ctx->sort_counters.ensure(sort_scratch_words(std::max<size_t>(sort_n, 1)) * 4));
     HIPCHECK(ctx->row_tab.ensure(frame_tables(nullptr, tiles_w, tiles_h).total_words * 4));
     const FrameTables tab = frame_tables(ctx->row_tab.as<uint32_t>(), tiles_w, tiles_h);
@@ -349,7 +349,7 @@ int run_sort(forma_hip_ctx* ctx, const uint64_t* src, DevCount nc, bool timing, 
     ctx->n_passes = 0;
     const size_t n = nc.bound;
     if (n >= (1ull << 30)) return fail(ctx, FORMA_E_CAPACITY, "more than 2^30-1 pixel segments on one device");
-    if (digit_bits == 0) digit_bits = ctx->digit_bits;
+    if (digit_bits == 0) digit_bits = ctx->digit_bits();
     HIPCHECK(ctx->seg_a.ensure((std::max<size_t>(n, 1) + SEG_PAD) * 8));
     HIPCHECK(ctx->seg_b.ensure((std::max<size_t>(n, 1) + SEG_PAD) * 8));
     HIPCHECK(ctx->sort_counters.ensure(sort_scratch_words(std::max<size_t>(n, 1)) * 4));
@@ -397,7 +397,7 @@ int verify_speculation(forma_hip_ctx* ctx) {
     const uint64_t live = (k_or ^ k_and) & 0xFFFFFFFFFFFull;
     const bool sorted = ctx->h_info->layer_unsorted == 0;
     const bool wrong = ctx->speculated && (live != ctx->live44 || sorted != ctx->layer_sorted);
-    ctx->pred_valid = true; ctx->pred_live44 = live; ctx->pred_layer_sorted = sorted;
+    ctx->learned.pred_valid = true; ctx->learned.pred_live44 = live; ctx->learned.pred_layer_sorted = sorted;
     return wrong ? FORMA_RETRY : FORMA_OK;
 }
 
@@ -488,9 +488,9 @@ static uint32_t slices_for(uint32_t per_cu_budget, uint32_t rows_painted, uint32
 // (the 512-lane variant for light rows in one slice — the 8K triangle scene — has the room as well: 32 KB of covers, two
 //  workgroups per CU instead of three, still one round for 512 rows)
 static bool covl_choice(const forma_hip_ctx* ctx, const CarryPlan& cp, uint32_t slices, bool async) {
-    const uint32_t mxr = ctx->pred_max_row;
+    const uint32_t mxr = ctx->learned.pred_max_row;
     const bool big = !cp.small && !cp.half && mxr != 0xFFFFFFFFu &&
-                     (async ? !ctx->covl_banned && (uint64_t)mxr + mxr / 64u <= carry_rows_covl_cap() : mxr <= carry_rows_covl_cap());
+                     (async ? !ctx->learned.covl_banned && (uint64_t)mxr + mxr / 64u <= carry_rows_covl_cap() : mxr <= carry_rows_covl_cap());
     return cp.local_sort && slices == 1u && ctx->dbg.carry_covl != 0 && (big || (cp.small && cp.half && (ctx->dbg.carry_covl & 2) == 0));
 }
 // the plan before any run is counted: a read-back-free frame (bound_j != 0) decides from the last verified frame
@@ -498,7 +498,7 @@ CarryPlan plan_carry(forma_hip_ctx* ctx, const PaintArgs& a, size_t n, uint32_t 
     CarryPlan cp{};
     // the rows' runs are ordered inside k_carry_rows when they fit its LDS; else by a global sort
     // (the in-LDS key holds 16 layer bits: every order a geom can produce has to fit, not just the style table)
-    cp.local_sort = ctx->n_orders <= 65536 && ctx->max_geom_order < 65536 && !ctx->global_runsort;
+    cp.local_sort = ctx->scene.n_orders <= 65536 && ctx->scene.max_geom_order < 65536 && !ctx->dbg.global_runsort;
     // A read-back-free frame whose rows are ordered in LDS needs no dense run numbering (the global run sort does): its runs are
     // found by ONE kernel, numbered per tile row from the index of the row's first segment (launch_runs' chain) — no counting
     // pass, the sorted stream is read once less.  The record arrays are then indexed like the segments: provisioned for N.
@@ -507,7 +507,7 @@ CarryPlan plan_carry(forma_hip_ctx* ctx, const PaintArgs& a, size_t n, uint32_t 
     // rounds of workgroups pays it in every round (4K: 23.8 + 52.8 -> 84.8 us, 8K: 16.4 + 31.0 -> 54.5) — those keep the counting pass.
     // With several frames in flight the waves that wait take issue slots from the other frames' kernels (1080p, three slots:
     // 9 942 -> 9 707 frames/s while the call alone gains 2.6 %): one frame in flight only, like the strip painters.
-    cp.chain = bound_j != 0 && n > 0 && cp.local_sort && ctx->pred_max_row <= carry_rows_local_cap() &&
+    cp.chain = bound_j != 0 && n > 0 && cp.local_sort && ctx->learned.pred_max_row <= carry_rows_local_cap() &&
                (ctx->dbg.runs_chain < 0 ? (RUNS_CHAIN_DEFAULT != 0 && runs_chain_words(n) <= RUNS_CHAIN_MAX_TILES && one_frame_in_flight(ctx))
                                         : ctx->dbg.runs_chain != 0);
     cp.chain_zero = cp.chain && ctx->pz.chain_p == ctx->runs_scratch.p && ctx->pz.chain_words >= runs_chain_words(n);
@@ -521,15 +521,15 @@ CarryPlan plan_carry(forma_hip_ctx* ctx, const PaintArgs& a, size_t n, uint32_t 
     ctx->cur_rows_painted = cp.rows_painted;
     cp.n_slices = 1;
     if (bound_j) {
-        cp.local_sort = cp.local_sort && ctx->pred_max_row <= carry_rows_local_cap();     // wrong guess -> plan_bad -> synchronous re-run
-        const uint32_t pmr = ctx->pred_max_row == 0xFFFFFFFFu ? 0u : ctx->pred_max_row;
+        cp.local_sort = cp.local_sort && ctx->learned.pred_max_row <= carry_rows_local_cap();     // wrong guess -> plan_bad -> synchronous re-run
+        const uint32_t pmr = ctx->learned.pred_max_row == 0xFFFFFFFFu ? 0u : ctx->learned.pred_max_row;
         cp.n_slices = slices_for(256u, cp.rows_painted, pmr);
         const uint32_t ks = slices_for(512u, cp.rows_painted, pmr);
         // (a whole 4K frame — 135 rows, one workgroup each — gains nothing from three small workgroups per row and its painters
         //  pay for the extra span lists: measured 124 -> 126 us carry, 133 -> 139 us paint; bands of <= 128 rows do gain)
-        if (cp.local_sort && ks > 1u && cp.rows_painted <= 128u && !ctx->small_banned && !ctx->no_small_carry && !ctx->force_slices) {
-            const bool known = ctx->pred_slice_n == ks && ctx->pred_slice_small;
-            const uint64_t guess = known ? (uint64_t)ctx->pred_max_slice * 10 / 9 : (uint64_t)ctx->pred_max_row * 5 / (3 * ks);
+        if (cp.local_sort && ks > 1u && cp.rows_painted <= 128u && !ctx->learned.small_banned && !ctx->dbg.no_small_carry && !ctx->force_slices()) {
+            const bool known = ctx->learned.pred_slice_n == ks && ctx->learned.pred_slice_small;
+            const uint64_t guess = known ? (uint64_t)ctx->learned.pred_max_slice * 10 / 9 : (uint64_t)ctx->learned.pred_max_row * 5 / (3 * ks);
             if (guess <= carry_rows_small_cap()) { cp.small = true; cp.n_slices = ks; }
             // ... as 512-lane workgroups when the slices fit those AND the frame is many workgroups (the painters see the same ks
             // span lists either way).  Two measurements stand behind the count: 1080p, 68 rows x 3 slices of ~900 runs: 36.1 -> 27.3 us,
@@ -542,11 +542,11 @@ CarryPlan plan_carry(forma_hip_ctx* ctx, const PaintArgs& a, size_t n, uint32_t 
         // at once instead of 256, each without the large variant's 148 KB of LDS to itself (carry 57 -> 32 us on the 8K scene,
         // 42 -> 27 at 1080p).  Heavy rows (the 4K scene: 4 800 runs) gain nothing from 3-6 half workgroups per row — measured:
         // the carry kernel saves 0-12 us and the painters pay as much for the extra span lists.
-        if (!cp.small && cp.local_sort && !ctx->small_banned && !ctx->no_small_carry && !ctx->force_slices && ctx->dbg.carry_half != 0 && pmr) {
+        if (!cp.small && cp.local_sort && !ctx->learned.small_banned && !ctx->dbg.no_small_carry && !ctx->force_slices() && ctx->dbg.carry_half != 0 && pmr) {
             uint32_t kh = 1u;
             if (ctx->dbg.carry_half > 1) kh = (uint32_t)std::min<int>(ctx->dbg.carry_half, (int)CR_MAX_SLICES_HOST);   // (tools: N slices per row)
-            const bool known = ctx->pred_slice_n == kh && ctx->pred_slice_small && ctx->pred_slice_half;
-            const uint64_t guess = known ? (uint64_t)ctx->pred_max_slice * 10 / 9 : (kh > 1u ? (uint64_t)pmr * 5 / (3 * kh) : (uint64_t)pmr * 6 / 5);
+            const bool known = ctx->learned.pred_slice_n == kh && ctx->learned.pred_slice_small && ctx->learned.pred_slice_half;
+            const uint64_t guess = known ? (uint64_t)ctx->learned.pred_max_slice * 10 / 9 : (kh > 1u ? (uint64_t)pmr * 5 / (3 * kh) : (uint64_t)pmr * 6 / 5);
             if (guess <= carry_rows_half_cap()) { cp.small = true; cp.half = true; cp.n_slices = kh; }
         }
         ctx->small_tried = cp.small;
@@ -554,7 +554,7 @@ CarryPlan plan_carry(forma_hip_ctx* ctx, const PaintArgs& a, size_t n, uint32_t 
     // BLOCKS (launch_runs, k_carry_rows): a read-back-free frame whose tile rows take ONE carry workgroup each needs neither the counting
     // pass nor the chain: the run kernel numbers per 2 048-segment tile into sparse arrays and the row's workgroup compacts them.
     // (... and takes a COVL variant of the carry kernel — settle_carry decides it, from the same predictions)
-    const uint32_t ns_final = ctx->force_slices ? std::min<uint32_t>(ctx->force_slices, CR_MAX_SLICES_HOST) : cp.n_slices;
+    const uint32_t ns_final = ctx->force_slices() ? ctx->force_slices() : cp.n_slices;
     // Measured (profiles/r06_experiments.txt, r6n-r6v): the 4K scene (135 heavy rows, a CU each) runs + carry 112.8 -> 94.1 us, frames/s per
     // call +3.9 %, three slots +3.8 %; the 8K triangle scene (512 light rows, two workgroups per CU) 72 -> 73 us — the head counts are one
     // more dependent round trip at the start of k_carry_rows, and with every workgroup of a full chip asking at once that costs what
@@ -568,13 +568,13 @@ CarryPlan plan_carry(forma_hip_ctx* ctx, const PaintArgs& a, size_t n, uint32_t 
 }
 // a synchronous frame after its count: the heaviest painted row is known
 void replan_carry(forma_hip_ctx* ctx, CarryPlan* cp, uint32_t max_row) {
-    ctx->pred_max_row = max_row;
+    ctx->learned.pred_max_row = max_row;
     cp->local_sort = cp->local_sort && max_row <= carry_rows_local_cap();
     cp->n_slices = slices_for(256u, cp->rows_painted, max_row);
 }
 // the final slice count and the COVL choice with it, once the frame has runs
 void settle_carry(forma_hip_ctx* ctx, CarryPlan* cp, uint32_t bound_j) {
-    if (ctx->force_slices) cp->n_slices = ctx->force_slices;  // FORMA_HIP_DEBUG=carry_slices (tests: every slice count on one GPU)
+    if (ctx->force_slices()) cp->n_slices = ctx->force_slices();  // FORMA_HIP_DEBUG=carry_slices (tests: every slice count on one GPU)
     ctx->cur_slices = cp->n_slices; ctx->cur_small = cp->small; ctx->cur_half = cp->half;
     cp->covl = covl_choice(ctx, *cp, cp->n_slices, bound_j != 0);
     ctx->covl_tried = cp->covl && bound_j != 0;
@@ -600,8 +600,8 @@ int number_runs(forma_hip_ctx* ctx, DevCount nc, const PaintArgs& a, const Frame
                     ctx->rk_u.as<uint64_t>(), ctx->blk_edge.as<BlkEdge>(), tab,
                     ctx->runs_scratch.as<uint32_t>(), dinfo, /*verify_plan=*/bound_j != 0 && ctx->speculated, ctx->live44,
                     ctx->layer_sorted, ctx->pending_masks,
-                    RunStyle{ctx->layer_sf.as<uint32_t>(), (uint32_t)ctx->n_orders,
-                             (a.cache_id >= 0 && ctx->have_unchanged) ? ctx->unchanged.as<uint8_t>() : nullptr,
+                    RunStyle{ctx->layer_sf.as<uint32_t>(), (uint32_t)ctx->scene.n_orders,
+                             (a.cache_id >= 0 && ctx->scene.have_unchanged) ? ctx->unchanged.as<uint8_t>() : nullptr,
                              blk ? ctx->run_lt_sp.as<uint32_t>() : ctx->run_lt.as<uint32_t>()},
                     tables_zero, ctx->sort_range, ctx->sort_range_n, what, chain ? tab.row_base : (blk ? ctx->row_sp.as<uint32_t>() : nullptr), cp->chain_zero, blk);
     };
@@ -662,14 +662,14 @@ int provision_spans(forma_hip_ctx* ctx, DevCount jc, uint32_t tiles_w, uint32_t 
     HIPCHECK(ctx->span_cov.ensure(jb * 16));
     // (a frame whose rows hold few spans skips them altogether — the painters would load a table to learn "none": +10 us
     //  on the 8192 x 8192 triangle scene; the first frame of a geometry does not know and goes without)
-    if (!ctx->no_span_groups && (ctx->force_span_groups || ctx->pred_row_spans > SPAN_GROUP_MIN_ROW)) {
+    if (!ctx->dbg.no_span_groups && (ctx->dbg.span_groups || ctx->learned.pred_row_spans > SPAN_GROUP_MIN_ROW)) {
         // the row's spans again by tile-column group: a pool of two entries per run (a span has a run to its left, and spans
         // longer than a group are the exception); a slice of a row that does not fit keeps only its row list
         const uint32_t n_groups = (tiles_w + SPAN_GROUP_TILES - 1u) >> SPAN_GROUP_SHIFT;
         const size_t pool = std::min<size_t>(2 * jb, 0xFFFFFFFFu);
         HIPCHECK(ctx->grp_tab.ensure((size_t)tiles_h * CR_MAX_SLICES_HOST * n_groups * sizeof(uint2)));
         HIPCHECK(ctx->grp_list.ensure(pool * sizeof(uint4)));
-        *groups = SpanGroups{ctx->grp_tab.as<uint2>(), ctx->grp_list.as<uint4>(), (uint32_t)pool, ctx->force_span_groups ? 0u : SPAN_GROUP_MIN_ROW};
+        *groups = SpanGroups{ctx->grp_tab.as<uint2>(), ctx->grp_list.as<uint4>(), (uint32_t)pool, ctx->dbg.span_groups ? 0u : SPAN_GROUP_MIN_ROW};
     }
     if (!local_sort) {
         HIPCHECK(ctx->rk_a.ensure(jb * 8));
@@ -678,9 +678,9 @@ int provision_spans(forma_hip_ctx* ctx, DevCount jc, uint32_t tiles_w, uint32_t 
         // (tile_y, layer) order: stable radix sort on bits 32..63 = [layer 21 | tile_y+1 11]; live bits come from the
         // rasterizer's varying-bit mask (layer = key bits 0..20, tile_y = key bits 33..43)
         uint64_t live = ((ctx->live44 & 0x1FFFFFull) | ((ctx->live44 >> 33) << 21)) << 32;
-        const SortPlan rk_plan = make_sort_plan(live, 32, 64, ctx->digit_bits);
+        const SortPlan rk_plan = make_sort_plan(live, 32, 64, ctx->digit_bits());
         *sorted_keys = launch_radix_sort(ctx->stream, ctx->rk_u.as<uint64_t>(), ctx->rk_a.as<uint64_t>(),
-                                         ctx->rk_b.as<uint64_t>(), jc, rk_plan, ctx->digit_bits,
+                                         ctx->rk_b.as<uint64_t>(), jc, rk_plan, ctx->digit_bits(),
                                          ctx->sort_counters.as<uint32_t>(), &ctx->info.as<FrameInfo>()->error, nullptr, nullptr);
         ctx->pz.sort_p = nullptr;
     }
@@ -697,7 +697,7 @@ PaintParams paint_params(const forma_hip_ctx* ctx, const PaintArgs& a, uint32_t 
         for (int i = 0; i < 4; i++) if (ch[i] == FORMA_CH_ALPHA) ch[i] = FORMA_CH_ONE;
     P.channels = (uint32_t)ch[0] | ((uint32_t)ch[1] << 8) | ((uint32_t)ch[2] << 16) | ((uint32_t)ch[3] << 24);
     for (int i = 0; i < 4; i++) P.clear[i] = a.clear[i];
-    P.stride_px = a.target ? (uint32_t)(a.target_pitch / (a.fmt == FORMA_FORMAT_LINEAR_F16 ? 8u : 4u)) : a.width; P.scene_has_clips = ctx->scene_has_clips ? 1u : 0u; P.scene_simple = ctx->scene_simple ? 1u : 0u; P.n_orders = (uint32_t)ctx->n_orders; P.n_words = (uint32_t)ctx->n_words;
+    P.stride_px = a.target ? (uint32_t)(a.target_pitch / (a.fmt == FORMA_FORMAT_LINEAR_F16 ? 8u : 4u)) : a.width; P.scene_has_clips = ctx->scene.scene_has_clips ? 1u : 0u; P.scene_simple = ctx->scene.scene_simple ? 1u : 0u; P.n_orders = (uint32_t)ctx->scene.n_orders; P.n_words = (uint32_t)ctx->scene.n_words;
     P.clear_unchanged = clear_unchanged;
     P.n_slices = n_slices;
     P.n_groups = (P.tiles_w + SPAN_GROUP_TILES - 1u) >> SPAN_GROUP_SHIFT;
@@ -705,7 +705,7 @@ PaintParams paint_params(const forma_hip_ctx* ctx, const PaintArgs& a, uint32_t 
     // ... and only for a geometry whose tiles have been seen to overflow the wave painter's lists (k_paint_deep ran): that is where
     // culling pays — 1080p cubics: painter 85 -> 24 us — while a scene of moderate lists (the 4K stand-in: 39 entries per tile,
     // phases bound by their dependent steps, not by the entries) only pays for the occluder scan, ~1 % of its frames/s.
-    P.cull = a.cache_id < 0 && !ctx->scene_has_clips && !ctx->dbg.no_cull && (ctx->cull_on || ctx->dbg.force_cull) ? 1u : 0u;
+    P.cull = a.cache_id < 0 && !ctx->scene.scene_has_clips && !ctx->dbg.no_cull && (ctx->learned.cull_on || ctx->dbg.force_cull) ? 1u : 0u;
     P.row_base = rows ? rows->row_base : nullptr; P.row_cnt = rows ? rows->row_count : nullptr;
     return P;
 }
@@ -713,32 +713,32 @@ PaintParams paint_params(const forma_hip_ctx* ctx, const PaintArgs& a, uint32_t 
 int heavy_order(forma_hip_ctx* ctx, const PaintArgs& a, uint32_t bound_j, DevCount jc, const FrameTables& tab, uint32_t tiles_painted,
                 bool strips, bool quads, int split_n, PaintParams* P) {
     ctx->order_pending = -1; ctx->order_cnt_dev = nullptr; ctx->order_keep_dev = nullptr;
-    if (ctx->dbg.order_thr >= 0) ctx->order_off = 0;
-    if (ctx->order_off) ctx->order_off--;                 // (a flat scene: the order is retried every 256 frames)
+    if (ctx->dbg.order_thr >= 0) ctx->learned.order_off = 0;
+    if (ctx->learned.order_off) ctx->learned.order_off--;                 // (a flat scene: the order is retried every 256 frames)
     // ... of launches that are a handful of rounds of wavefronts: one tile's life is then a good part of the launch's.  A frame
     // of 32 rounds (the 8K scene: 262 144 tiles on 8 192 wave slots) has no tail worth 10 % of bookkeeping.
-    if (!(ctx->order_enable && bound_j && a.cache_id < 0 && !strips && !quads && !ctx->dbg.no_order && jc.bound > 0 && tiles_painted && !ctx->order_off && split_n == 0 &&
-          tiles_painted <= 16u * paint_strip_tiles(ctx) && (one_frame_in_flight(ctx) || ctx->dbg.order_thr >= 0))) { ctx->order_cur = -1; return FORMA_OK; }   // (any other frame in between: the lists are stale)
+    if (!(ctx->order_enable && bound_j && a.cache_id < 0 && !strips && !quads && !ctx->dbg.no_order && jc.bound > 0 && tiles_painted && !ctx->learned.order_off && split_n == 0 &&
+          tiles_painted <= 16u * paint_strip_tiles(ctx) && (one_frame_in_flight(ctx) || ctx->dbg.order_thr >= 0))) { ctx->learned.order_cur = -1; return FORMA_OK; }   // (any other frame in between: the lists are stale)
     // (heavy section: an eighth of the band's tiles, as PAINT_ORDER_SUBS lists of equal capacity)
     const size_t per = paint_band_tiles(P->crop_y1 > P->crop_y0 ? P->crop_y1 - P->crop_y0 : 0u, P->tiles_w), hcap = std::max<size_t>((per / 8 + PAINT_ORDER_SUBS - 1) / PAINT_ORDER_SUBS, 2) * PAINT_ORDER_SUBS;
     const size_t set_words = PAINT_ORDER_WORDS + 8 * hcap + (8 * per + 3) / 4;      // counts | lists | one flag byte per tile
     if (ctx->order_buf.cap < 2 * set_words * 4) {
         HIPCHECK(ctx->order_buf.ensure(2 * set_words * 4));
         HIPCHECK(hipMemsetAsync(ctx->order_buf.p, 0, ctx->order_buf.cap, ctx->stream));   // (flag bytes nobody has written yet say "not heavy")
-        ctx->order_cur = -1;
+        ctx->learned.order_cur = -1;
     }
-    const forma_hip_ctx::OrderSig sig{P->tiles_w, P->tiles_h, P->crop_x0, P->crop_x1, P->crop_y0, P->crop_y1};
+    const Learned::OrderSig sig{P->tiles_w, P->tiles_h, P->crop_x0, P->crop_x1, P->crop_y0, P->crop_y1};
     uint32_t* base = ctx->order_buf.as<uint32_t>();
-    if (ctx->order_cur >= 0 && !(ctx->order_sig == sig)) ctx->order_cur = -1;
-    const int w = ctx->order_cur == 0 ? 1 : 0;
-    if (ctx->order_cur >= 0) {
-        P->order_cnt_in = base + (size_t)ctx->order_cur * set_words; P->order_list_in = P->order_cnt_in + PAINT_ORDER_WORDS;
+    if (ctx->learned.order_cur >= 0 && !(ctx->learned.order_sig == sig)) ctx->learned.order_cur = -1;
+    const int w = ctx->learned.order_cur == 0 ? 1 : 0;
+    if (ctx->learned.order_cur >= 0) {
+        P->order_cnt_in = base + (size_t)ctx->learned.order_cur * set_words; P->order_list_in = P->order_cnt_in + PAINT_ORDER_WORDS;
         P->order_flag_in = reinterpret_cast<const uint8_t*>(P->order_list_in + 8 * hcap);
     }
     uint32_t* wset = base + (size_t)w * set_words;
     P->order_cnt_out = tab.order_cnt; P->order_list_out = wset + PAINT_ORDER_WORDS;
     P->order_flag_out = reinterpret_cast<uint8_t*>(wset + PAINT_ORDER_WORDS + 8 * hcap);
-    P->order_hcap = (uint32_t)hcap; P->order_thr = ctx->dbg.order_thr >= 0 ? (uint32_t)ctx->dbg.order_thr : ctx->order_thr;
+    P->order_hcap = (uint32_t)hcap; P->order_thr = ctx->dbg.order_thr >= 0 ? (uint32_t)ctx->dbg.order_thr : ctx->learned.order_thr;
     ctx->order_pending = w; ctx->order_pending_sig = sig; ctx->order_tiles = tiles_painted;
     ctx->order_cnt_dev = tab.order_cnt; ctx->order_keep_dev = wset;
     return FORMA_OK;
@@ -753,12 +753,12 @@ void launch_carry(forma_hip_ctx* ctx, const PaintArgs& a, const PaintParams& P, 
         if (i < 3 ? sel == FORMA_CH_ALPHA : colour) fold_equals_paint = false;
     }
     uint32_t bin_shift = 0;                               // 256 layer bins over the orders in use
-    while (bin_shift < 16 && (((uint64_t)std::max<size_t>(ctx->n_orders, 1) - 1) >> bin_shift) > 255) bin_shift++;
+    while (bin_shift < 16 && (((uint64_t)std::max<size_t>(ctx->scene.n_orders, 1) - 1) >> bin_shift) > 255) bin_shift++;
     launch_carry_rows(ctx->stream, cp.local_sort, cp.small, cp.half, cp.n_slices, bin_shift, sorted_keys, ctx->records.as<TileRecord>(),
                       ctx->blk_edge.as<BlkEdge>(), nc, jc, ctx->layer_sf.as<uint32_t>(),
-                      (uint32_t)ctx->n_orders, P.tiles_w, P.tiles_h, tab.row_count, tab.row_span_lo,
+                      (uint32_t)ctx->scene.n_orders, P.tiles_w, P.tiles_h, tab.row_count, tab.row_span_lo,
                       tab.row_span_cnt, ctx->span_key.as<uint64_t>(), ctx->span_cov.as<uint4>(),
-                      (a.cache_id >= 0 && ctx->have_unchanged) ? ctx->unchanged.as<uint8_t>() : nullptr, ctx->info.as<FrameInfo>(),
+                      (a.cache_id >= 0 && ctx->scene.have_unchanged) ? ctx->unchanged.as<uint8_t>() : nullptr, ctx->info.as<FrameInfo>(),
                       runs_edge_segments(),
                       // invisible carries of a partial last tile row are dropped only when nothing can observe them: with a
                       // buffer-layer cache the layer count of a tile is state (passes/tile_unchanged.rs)
@@ -788,7 +788,7 @@ PaintInputs paint_inputs(forma_hip_ctx* ctx, const FrameTables& tab, DevCount jc
 int run_paint(forma_hip_ctx* ctx, DevCount nc, const PaintArgs& a, bool timing, uint32_t bound_j = 0) {
     const size_t n = nc.bound;
     // set_styles and set_images are separate calls: the image a texture style names is checked where both are known
-    if (ctx->any_texture && ctx->max_image_index >= ctx->n_images) return fail(ctx, FORMA_E_ARG, "texture style names an image that was not uploaded");
+    if (ctx->scene.any_texture && ctx->scene.max_image_index >= ctx->scene.n_images) return fail(ctx, FORMA_E_ARG, "texture style names an image that was not uploaded");
     const uint32_t tiles_w = a.tiles_w(), tiles_h = a.tiles_h();
     ctx->img_w = a.width; ctx->img_h = a.height;
     ctx->chain_rows = nullptr; ctx->n_chain_rows = 0;
@@ -819,7 +819,7 @@ int run_paint(forma_hip_ctx* ctx, DevCount nc, const PaintArgs& a, bool timing, 
     if ((rc = heavy_order(ctx, a, bound_j, jc, tab, tiles_painted, strips, quads, split_n, &P))) return rc;
     // the (empty) k_paint_deep launch costs ~5 us of every frame: a read-back-free frame without a cache skips it when the
     // last verified frame had no deep tile; a tile that needs it then voids the frame (re-run in full)
-    const bool launch_deep = !(bound_j != 0 && a.cache_id < 0 && ctx->pred_no_deep);
+    const bool launch_deep = !(bound_j != 0 && a.cache_id < 0 && ctx->learned.pred_no_deep);
     if (jc.bound > 0) launch_carry(ctx, a, P, tab, cp, nc, jc, groups, sorted_keys);
     stage_end(ctx, ST_CARRY, timing);
     stage_begin(ctx, ST_PAINT, timing);
@@ -957,12 +957,8 @@ int copy_image_out(forma_hip_ctx* ctx, uint8_t* dst, size_t stride, bool timing,
     }
     // cache attached: which tiles were written?
     const size_t T = (size_t)tiles_w * tiles_h;
-    if (ctx->h_written_cap < T) {
-        if (ctx->h_written) (void)hipHostFree(ctx->h_written);
-        ctx->h_written = nullptr; ctx->h_written_cap = 0;
-        HIPCHECK(hipHostMalloc((void**)&ctx->h_written, T, hipHostMallocDefault));
-        ctx->h_written_cap = T;
-    }
+    HIPCHECK(ctx->h_written.ensure(T));
+    const uint8_t* written = ctx->h_written.as<uint8_t>();
     // While the flags travel, the device packs the written tiles' pixels (list order = row-major over the crop): a frame that
     // rewrote 1.5 % of a 4K canvas then moves 0.5 MB over PCIe instead of 33 MB.  More than a quarter of the crop written:
     // one strided copy of the crop through the staging image is cheaper than the per-tile scatter on the host.
@@ -974,51 +970,41 @@ int copy_image_out(forma_hip_ctx* ctx, uint8_t* dst, size_t stride, bool timing,
     launch_pack_written(ctx->stream, ctx->cache_written.as<uint8_t>(), tiles_w, tx0, tx1, ty0, ty1, ctx->pack_list.as<uint32_t>() + 1,
                         ctx->pack_list.as<uint32_t>(), max_pack, ctx->cur_image, a.width, a.height, ctx->pack_pix.as<uint32_t>());
     HIPCHECK(hipGetLastError());
-    HIPCHECK(hipMemcpyAsync(ctx->h_written, ctx->cache_written.p, T, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHECK(hipMemcpyAsync(ctx->h_written.p, ctx->cache_written.p, T, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHECK(hipStreamSynchronize(ctx->stream));
     ctx->lw_flags_on_host = true;
     size_t n_written = 0;
-    for (uint32_t ty = ty0; ty < ty1; ty++) for (uint32_t tx = tx0; tx < tx1; tx++) n_written += ctx->h_written[(size_t)ty * tiles_w + tx] ? 1 : 0;
+    for (uint32_t ty = ty0; ty < ty1; ty++) for (uint32_t tx = tx0; tx < tx1; tx++) n_written += written[(size_t)ty * tiles_w + tx] ? 1 : 0;
     ctx->last_written = (uint32_t)n_written;
     if (n_written == n_crop) {                                         // everything was painted: one strided copy
         { const int rc = copy_rows_out(ctx, ctx->stream, dst, stride, px0, px1, py0, py1, a.width); if (rc) return rc; }
     } else if (n_written && n_written <= max_pack) {                   // the packed tiles, then each into its place
         const size_t bytes = n_written * 1024;
-        if (ctx->h_stage_cap < bytes) {
-            if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
-            ctx->h_stage = nullptr; ctx->h_stage_cap = 0;
-            HIPCHECK(hipHostMalloc((void**)&ctx->h_stage, std::max<size_t>(bytes, 1 << 20), hipHostMallocDefault));
-            ctx->h_stage_cap = std::max<size_t>(bytes, 1 << 20);
-        }
-        HIPCHECK(hipMemcpyAsync(ctx->h_stage, ctx->pack_pix.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHECK(ctx->h_stage.ensure(bytes, 1 << 20));
+        HIPCHECK(hipMemcpyAsync(ctx->h_stage.p, ctx->pack_pix.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHECK(hipStreamSynchronize(ctx->stream));
         size_t k = 0;
         for (uint32_t ty = ty0; ty < ty1; ty++)
             for (uint32_t tx = tx0; tx < tx1; tx++) {
-                if (!ctx->h_written[(size_t)ty * tiles_w + tx]) continue;
+                if (!written[(size_t)ty * tiles_w + tx]) continue;
                 const size_t x0 = (size_t)tx * 16, x1 = std::min<size_t>(x0 + 16, a.width);
                 const size_t y0 = (size_t)ty * 16, y1 = std::min<size_t>(y0 + 16, a.height);
-                const uint8_t* src = ctx->h_stage + k * 1024;
+                const uint8_t* src = ctx->h_stage.as<uint8_t>() + k * 1024;
                 for (size_t y = y0; y < y1; y++) memcpy(dst + y * stride + x0 * 4, src + (y - y0) * 64, (x1 - x0) * 4);
                 k++;
             }
     } else if (n_written) {                                            // stage, then copy only the written tiles
         const size_t bytes = pitch * a.height;
-        if (ctx->h_stage_cap < bytes) {
-            if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
-            ctx->h_stage = nullptr; ctx->h_stage_cap = 0;
-            HIPCHECK(hipHostMalloc((void**)&ctx->h_stage, bytes, hipHostMallocDefault));
-            ctx->h_stage_cap = bytes;
-        }
-        HIPCHECK(hipMemcpy2DAsync(ctx->h_stage + py0 * pitch + px0 * 4, pitch, ctx->cur_image + py0 * pitch + px0 * 4, pitch,
+        HIPCHECK(ctx->h_stage.ensure(bytes));
+        HIPCHECK(hipMemcpy2DAsync(ctx->h_stage.as<uint8_t>() + py0 * pitch + px0 * 4, pitch, ctx->cur_image + py0 * pitch + px0 * 4, pitch,
                                   (px1 - px0) * 4, py1 - py0, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHECK(hipStreamSynchronize(ctx->stream));
         for (uint32_t ty = ty0; ty < ty1; ty++)
             for (uint32_t tx = tx0; tx < tx1; tx++) {
-                if (!ctx->h_written[(size_t)ty * tiles_w + tx]) continue;
+                if (!written[(size_t)ty * tiles_w + tx]) continue;
                 const size_t x0 = (size_t)tx * 16, x1 = std::min<size_t>(x0 + 16, a.width);
                 const size_t y0 = (size_t)ty * 16, y1 = std::min<size_t>(y0 + 16, a.height);
-                for (size_t y = y0; y < y1; y++) memcpy(dst + y * stride + x0 * 4, ctx->h_stage + y * pitch + x0 * 4, (x1 - x0) * 4);
+                for (size_t y = y0; y < y1; y++) memcpy(dst + y * stride + x0 * 4, ctx->h_stage.as<uint8_t>() + y * pitch + x0 * 4, (x1 - x0) * 4);
             }
     }
     stage_end(ctx, ST_D2H, timing);
@@ -1031,15 +1017,15 @@ int finish_frame(forma_hip_ctx* ctx, forma_timings_t* t, bool have_info = false)
         HIPCHECK(hipStreamSynchronize(ctx->stream));
     }
     // device-side invariant flags
-    ctx->pred_no_deep = !(ctx->h_info->error & 16u);       // (8, 16: bookkeeping bits, not errors)
-    if (ctx->h_info->error & 16u) ctx->cull_on = true;     // deep tiles: from now on the painters cull (until the geometry changes)
+    ctx->learned.pred_no_deep = !(ctx->h_info->error & 16u);       // (8, 16: bookkeeping bits, not errors)
+    if (ctx->h_info->error & 16u) ctx->learned.cull_on = true;     // deep tiles: from now on the painters cull (until the geometry changes)
     if (!ctx->h_info->plan_bad) {                          // what the keys' tile fields spanned (a sort that did not run leaves min > max)
         const uint32_t* r = ctx->h_info->tile_range;
-        ctx->pred_range = KeyRange{~r[0], r[1], ~r[2], r[3], true};
+        ctx->learned.pred_range = KeyRange{~r[0], r[1], ~r[2], r[3], true};
     }
-    if (!ctx->h_info->plan_bad) ctx->pred_row_spans = ctx->h_info->n_spans / ctx->cur_rows_painted;
-    if (!ctx->h_info->plan_bad && ctx->h_info->n_slices) ctx->pred_slice_len = std::max(ctx->h_info->n_segments / ctx->h_info->n_slices, 1u);
-    if (!ctx->h_info->plan_bad) { ctx->pred_max_slice = ctx->h_info->max_slice_runs; ctx->pred_slice_n = ctx->cur_slices; ctx->pred_slice_small = ctx->cur_small; ctx->pred_slice_half = ctx->cur_half; }
+    if (!ctx->h_info->plan_bad) ctx->learned.pred_row_spans = ctx->h_info->n_spans / ctx->cur_rows_painted;
+    if (!ctx->h_info->plan_bad && ctx->h_info->n_slices) ctx->learned.pred_slice_len = std::max(ctx->h_info->n_segments / ctx->h_info->n_slices, 1u);
+    if (!ctx->h_info->plan_bad) { ctx->learned.pred_max_slice = ctx->h_info->max_slice_runs; ctx->learned.pred_slice_n = ctx->cur_slices; ctx->learned.pred_slice_small = ctx->cur_small; ctx->learned.pred_slice_half = ctx->cur_half; }
     if ((ctx->h_info->error & ~24u) == 1u)                   // (bit 0: k_carry_rows met a run of a layer without a style)
         return fail(ctx, FORMA_E_ARG, "a geometry entry names an order that has no style (forma_hip_set_styles: offset FORMA_NONE or beyond the table)");
     if (ctx->h_info->error & ~24u) return fail(ctx, FORMA_E_INTERNAL, "device-side invariant violated");
@@ -1133,7 +1119,6 @@ int upload(forma_hip_ctx* ctx, DevBuf& b, const T* src, size_t n) {
 // order is the only ordering.  A slot has at most one frame in flight and is settled before its next one starts, so its
 // staging block is free again by then, and a frame that is voided and re-run finds the table it was enqueued with.
 inline forma_hip_ctx* tab_owner(forma_hip_ctx* c) { return c->owner ? c->owner : c; }
-inline std::vector<forma_hip_ctx*> tab_slots(forma_hip_ctx* o) { return o->slots.empty() ? std::vector<forma_hip_ctx*>{o} : o->slots; }
 
 // a scene call settles the frames in flight (counted when there were any)
 int scene_drain(forma_hip_ctx* ctx) {
@@ -1144,8 +1129,8 @@ int scene_drain(forma_hip_ctx* ctx) {
 // every slot gets its table, its record buffer and its page-locked staging block, sized for the table as it is (a block of
 // records never exceeds the table: the whole table is copied instead); the journal's vectors get their final capacity
 int tables_provision(forma_hip_ctx* o) {
-    const size_t table_bytes = std::max<size_t>(o->n_geoms, 1) * sizeof(forma_geom_t), cap = std::max<size_t>(table_bytes, 1024);
-    for (forma_hip_ctx* ctx : tab_slots(o)) {
+    const size_t table_bytes = std::max<size_t>(o->scene.n_geoms, 1) * sizeof(forma_geom_t), cap = std::max<size_t>(table_bytes, 1024);
+    for (forma_hip_ctx* ctx : frame_slots(o)) {
         HIPCHECK(hipSetDevice(ctx->device));
         const void* was = ctx->geoms_own.p;
         HIPCHECK(ctx->geoms_own.ensure(table_bytes));
@@ -1157,15 +1142,10 @@ int tables_provision(forma_hip_ctx* o) {
             o->geoms.borrow(o->geoms_own);
         }
         HIPCHECK(ctx->tab_blob.ensure(cap));
-        if (ctx->h_tab_stage_cap < cap) {
-            const size_t want = std::max(cap, ctx->h_tab_stage_cap + ctx->h_tab_stage_cap / 2);
-            if (ctx->h_tab_stage) { (void)hipHostFree(ctx->h_tab_stage); ctx->h_tab_stage = nullptr; ctx->h_tab_stage_cap = 0; }
-            HIPCHECK(hipHostMalloc((void**)&ctx->h_tab_stage, want, hipHostMallocDefault));
-            ctx->h_tab_stage_cap = want;
-        }
+        HIPCHECK(ctx->h_tab_stage.ensure(cap, 0, true));
     }
-    o->tab_ent_seq.resize(o->n_geoms, 0);
-    o->tab_ent_log.reserve(2 * o->n_geoms + 96);         // (below n_geoms + 64 items before a call, which adds one per slot at most)
+    o->tab_ent_seq.resize(o->scene.n_geoms, 0);
+    o->tab_ent_log.reserve(2 * o->scene.n_geoms + 96);         // (below n_geoms + 64 items before a call, which adds one per slot at most)
     o->tab_rng_log.reserve(64);
     return FORMA_OK;
 }
@@ -1177,12 +1157,12 @@ int tables_provision(forma_hip_ctx* o) {
 // when the slot, whose frame's tail has been seen, packs its next records).  tab_on is raised once every slot is seeded.
 int tables_enable(forma_hip_ctx* o) {
     forma_hip_ctx* ctx = o;
-    ctx->tab_ent_seq.assign(ctx->n_geoms, 0);
+    ctx->tab_ent_seq.assign(ctx->scene.n_geoms, 0);
     int rc = tables_provision(o);
     if (rc) return rc;
-    const size_t table_bytes = o->n_geoms * sizeof(forma_geom_t);
+    const size_t table_bytes = o->scene.n_geoms * sizeof(forma_geom_t);
     if (!o->geoms_shared.p) return fail(o, FORMA_E_INTERNAL, "layer table: no shared table to seed the frame slots from");
-    for (forma_hip_ctx* sl : tab_slots(o)) {
+    for (forma_hip_ctx* sl : frame_slots(o)) {
         ctx = sl;
         HIPCHECK(hipSetDevice(sl->device));
         HIPCHECK(hipMemcpyAsync(sl->geoms_own.p, o->geoms_shared.p, table_bytes, hipMemcpyDeviceToDevice, sl->stream));
@@ -1190,7 +1170,7 @@ int tables_enable(forma_hip_ctx* o) {
     ctx = o;
     o->tab_on = true;
     o->tab_seq = o->tab_full_seq = 1;
-    for (forma_hip_ctx* sl : tab_slots(o)) sl->tab_seen = 1;
+    for (forma_hip_ctx* sl : frame_slots(o)) sl->tab_seen = 1;
     HIPCHECK(hipSetDevice(o->device));
     share_scene(o);
     return FORMA_OK;
@@ -1200,7 +1180,7 @@ int tables_enable(forma_hip_ctx* o) {
 // "copy the whole table"
 void tables_recorded(forma_hip_ctx* o) {
     o->cnt.table_edits++;
-    if (o->tab_ent_log.size() >= o->n_geoms + 64 || o->tab_rng_log.size() >= 32) {
+    if (o->tab_ent_log.size() >= o->scene.n_geoms + 64 || o->tab_rng_log.size() >= 32) {
         o->tab_ent_log.clear(); o->tab_rng_log.clear();
         o->tab_full_seq = o->tab_seq;
     }
@@ -1211,7 +1191,7 @@ int tables_catch_up(forma_hip_ctx* ctx) {
     forma_hip_ctx* o = tab_owner(ctx);
     if (!o->tab_on || ctx->tab_seen == o->tab_seq) return FORMA_OK;
     HIPCHECK(hipSetDevice(ctx->device));
-    const uint32_t n = (uint32_t)o->n_geoms;
+    const uint32_t n = (uint32_t)o->scene.n_geoms;
     const size_t table_bytes = (size_t)n * sizeof(forma_geom_t);
     const uint64_t seen = ctx->tab_seen;
     if (n) {
@@ -1223,15 +1203,15 @@ int tables_catch_up(forma_hip_ctx* ctx) {
             n_rng = o->tab_rng_log.size() - r0;
             for (size_t i = e0; i < o->tab_ent_log.size(); i++) n_ent += o->tab_ent_seq[o->tab_ent_log[i].slot] == o->tab_ent_log[i].seq;
             const size_t rec_bytes = (n_rng + n_ent) * sizeof(GeomEditRec);
-            full = n_rng > 8 || (rec_bytes > table_bytes && rec_bytes > 1024) || rec_bytes > ctx->h_tab_stage_cap || rec_bytes > ctx->tab_blob.cap;
+            full = n_rng > 8 || (rec_bytes > table_bytes && rec_bytes > 1024) || rec_bytes > ctx->h_tab_stage.cap || rec_bytes > ctx->tab_blob.cap;
         }
         if (full) {
-            if (table_bytes > ctx->h_tab_stage_cap || table_bytes > ctx->geoms.cap) return fail(ctx, FORMA_E_INTERNAL, "layer table: a frame slot was not provisioned");
-            memcpy(ctx->h_tab_stage, o->h_tab.data(), table_bytes);
-            HIPCHECK(hipMemcpyAsync(ctx->geoms.p, ctx->h_tab_stage, table_bytes, hipMemcpyHostToDevice, ctx->stream));
+            if (table_bytes > ctx->h_tab_stage.cap || table_bytes > ctx->geoms.cap) return fail(ctx, FORMA_E_INTERNAL, "layer table: a frame slot was not provisioned");
+            memcpy(ctx->h_tab_stage.p, o->h_tab.data(), table_bytes);
+            HIPCHECK(hipMemcpyAsync(ctx->geoms.p, ctx->h_tab_stage.p, table_bytes, hipMemcpyHostToDevice, ctx->stream));
             o->cnt.table_edit_bytes_h2d += table_bytes;
         } else if (n_rng + n_ent) {
-            GeomEditRec* rec = reinterpret_cast<GeomEditRec*>(ctx->h_tab_stage);
+            GeomEditRec* rec = ctx->h_tab_stage.as<GeomEditRec>();
             size_t k = 0;
             for (size_t i = r0; i < o->tab_rng_log.size(); i++, k++) {
                 const forma_hip_ctx::TabRng& r = o->tab_rng_log[i];
@@ -1277,10 +1257,10 @@ int tables_catch_up(forma_hip_ctx* ctx) {
         if (ctx->seg_u_fused) { ctx->seg_u_fused = false; ctx->have_unsorted = false; }
     }
     ctx->tab_seen = o->tab_seq;
-    ctx->n_geoms = o->n_geoms; ctx->max_geom_order = o->tab_max_order;
+    ctx->scene.n_geoms = o->scene.n_geoms; ctx->scene.max_geom_order = o->tab_max_order;
     // the journal is trimmed to the slot that has seen least
     uint64_t oldest = o->tab_seq;
-    for (const forma_hip_ctx* sl : tab_slots(o)) oldest = std::min(oldest, sl->tab_seen);
+    for (const forma_hip_ctx* sl : frame_slots(o)) oldest = std::min(oldest, sl->tab_seen);
     size_t dr = 0, de = 0;
     while (dr < o->tab_rng_log.size() && o->tab_rng_log[dr].seq <= oldest) dr++;
     while (de < o->tab_ent_log.size() && o->tab_ent_log[de].seq <= oldest) de++;
@@ -1291,7 +1271,7 @@ int tables_catch_up(forma_hip_ctx* ctx) {
 
 // every slot up to date and its stream idle (multi-device contexts, whose frames do not start in render_on)
 int tables_sync_all(forma_hip_ctx* o) {
-    for (forma_hip_ctx* ctx : tab_slots(o)) {
+    for (forma_hip_ctx* ctx : frame_slots(o)) {
         HIPCHECK(hipSetDevice(ctx->device));
         HIPCHECK(hipStreamSynchronize(ctx->stream));                  // (the staging block may still be on its way: the first edit call)
         const int rc = tables_catch_up(ctx);
@@ -1336,14 +1316,6 @@ int forma_hip_create(forma_hip_ctx** out, int device) {
     ctx->device = device;
     ctx->n_cus = prop.multiProcessorCount > 0 ? (uint32_t)prop.multiProcessorCount : 256u;
     ctx->dbg = forma_debug_parse();                       // FORMA_HIP_DEBUG (debug.h): test / tool switches, never set in deployment
-    if (ctx->dbg.digit_bits == 4 || ctx->dbg.digit_bits == 8 || ctx->dbg.digit_bits == 9) ctx->digit_bits = ctx->dbg.digit_bits;
-    ctx->no_async = ctx->dbg.sync;
-    ctx->global_runsort = ctx->dbg.global_runsort;
-    ctx->xgather_always = ctx->dbg.xgather;
-    ctx->no_small_carry = ctx->dbg.no_small_carry;
-    ctx->no_span_groups = ctx->dbg.no_span_groups;
-    ctx->force_span_groups = ctx->dbg.span_groups;
-    if (ctx->dbg.carry_slices > 0) ctx->force_slices = (uint32_t)std::min(std::max(ctx->dbg.carry_slices, 1), (int)CR_MAX_SLICES_HOST);
     if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
         delete ctx; return FORMA_E_HIP;
     }
@@ -1399,11 +1371,8 @@ void forma_hip_destroy(forma_hip_ctx* ctx) {
     if (ctx->h_info) (void)hipHostFree(ctx->h_info);
     if (ctx->h_rows) (void)hipHostFree(ctx->h_rows);
     if (ctx->h_xlocal) (void)hipHostFree(ctx->h_xlocal);
-    if (ctx->h_written) (void)hipHostFree(ctx->h_written);
-    if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
-    if (ctx->h_geo) (void)hipHostFree(ctx->h_geo);
+    for (PinnedBuf* b : ctx->pinned_bufs()) b->release();
     ctx->geoms_own.release(); ctx->geoms_shared.release(); ctx->tab_blob.release();
-    if (ctx->h_tab_stage) (void)hipHostFree(ctx->h_tab_stage);
     for (auto& c : ctx->caches) { c.tiles.release(); c.image.release(); }
     for (auto& r : ctx->registered) (void)hipHostUnregister(r.first);
     if (ctx->copy_stream) {
@@ -1434,7 +1403,7 @@ int forma_hip_set_geometry(forma_hip_ctx* ctx, const float* x, const float* y, c
     if ((rc = upload(ctx, ctx->line_slot, line_slot, n_points ? n_points - 1 : 0))) return rc;   //  also once something is appended behind it)
     if (n_points) HIPCHECK(hipMemsetAsync(ctx->line_slot.as<uint32_t>() + (n_points - 1), 0xFF, 4, ctx->stream));
     HIPCHECK(hipStreamSynchronize(ctx->stream));
-    ctx->n_points = n_points;
+    ctx->scene.n_points = n_points;
     ctx->cnt.geometry_uploads++; ctx->cnt.geometry_bytes_h2d += n_points * 8 + (n_points ? n_points - 1 : 0) * 4;
     invalidate_counts(ctx);                               // new geometry: the next frame re-learns N and J synchronously
     share_scene(ctx);
@@ -1457,7 +1426,7 @@ int forma_hip_set_geoms(forma_hip_ctx* ctx, const forma_geom_t* geoms, size_t n_
     if ((rc = upload(ctx, ctx->geoms.borrowed ? ctx->geoms_own : ctx->geoms, geoms, n_geoms))) return rc;   // (edits in use: `geoms` is a view of geoms_own)
     if (ctx->geoms.borrowed) ctx->geoms.borrow(ctx->geoms_own);
     HIPCHECK(hipStreamSynchronize(ctx->stream));
-    ctx->n_geoms = n_geoms; ctx->max_geom_order = max_order;
+    ctx->scene.n_geoms = n_geoms; ctx->scene.max_geom_order = max_order;
     // the table on the host (forma_hip_read_geoms, the edit calls); once edits are in use the other frame slots own tables, which
     // take the whole of the new one when their next frame starts
     ctx->h_tab.assign(geoms, geoms + n_geoms); ctx->tab_max_order = max_order;
@@ -1468,8 +1437,7 @@ int forma_hip_set_geoms(forma_hip_ctx* ctx, const forma_geom_t* geoms, size_t n_
         HIPCHECK(hipSetDevice(ctx->device));
     }
     // (transforms move the lines: a fused frame's unsorted stream can no longer be rebuilt from them — restore_unsorted)
-    if (ctx->seg_u_fused) { ctx->seg_u_fused = false; ctx->have_unsorted = false; }
-    for (forma_hip_ctx* sl : ctx->slots) if (sl->seg_u_fused) { sl->seg_u_fused = false; sl->have_unsorted = false; }
+    for (forma_hip_ctx* sl : frame_slots(ctx)) if (sl->seg_u_fused) { sl->seg_u_fused = false; sl->have_unsorted = false; }
     share_scene(ctx);
     return FORMA_OK;
 }
@@ -1480,7 +1448,7 @@ int forma_hip_update_geoms(forma_hip_ctx* ctx, const uint32_t* slots, const form
     if (!slots || !entries) return fail(ctx, FORMA_E_ARG, "null slots / entries");
     if (ctx->multi) return multi_update_geoms(ctx, slots, entries, n);
     for (size_t i = 0; i < n; i++) {
-        if (slots[i] >= ctx->n_geoms) return fail(ctx, FORMA_E_ARG, "slot beyond the layer table (forma_hip_set_geoms sizes it)");
+        if (slots[i] >= ctx->scene.n_geoms) return fail(ctx, FORMA_E_ARG, "slot beyond the layer table (forma_hip_set_geoms sizes it)");
         if (entries[i].order != FORMA_NONE && entries[i].order > FORMA_LAYER_LIMIT) return fail(ctx, FORMA_E_ARG, "order exceeds LAYER_LIMIT");
     }
     if (!ctx->tab_on) { const int rc = tables_enable(ctx); if (rc) return rc; }
@@ -1507,7 +1475,7 @@ int forma_hip_update_geoms_xf(forma_hip_ctx* ctx, uint32_t first, uint32_t count
     if (!ctx) return FORMA_E_ARG;
     if (count == 0) return FORMA_OK;
     if (ctx->multi) return multi_update_geoms_xf(ctx, first, count, xf);
-    if ((uint64_t)first + count > ctx->n_geoms) return fail(ctx, FORMA_E_ARG, "range beyond the layer table (forma_hip_set_geoms sizes it)");
+    if ((uint64_t)first + count > ctx->scene.n_geoms) return fail(ctx, FORMA_E_ARG, "range beyond the layer table (forma_hip_set_geoms sizes it)");
     if (!ctx->tab_on) { const int rc = tables_enable(ctx); if (rc) return rc; }
     static const float identity[6] = {1.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f};
     forma_hip_ctx::TabRng r{++ctx->tab_seq, first, count, xf ? 1u : 0u, {0, 0, 0, 0, 0, 0}};
@@ -1529,7 +1497,7 @@ int forma_hip_update_geoms_xf(forma_hip_ctx* ctx, uint32_t first, uint32_t count
 int forma_hip_read_geoms(forma_hip_ctx* ctx, forma_geom_t* out, size_t capacity, size_t* out_n) {
     if (!ctx || !out_n) return fail(ctx, FORMA_E_ARG, "null out_n");
     if (ctx->multi) ctx = multi_first(ctx);
-    const size_t n = ctx->n_geoms;
+    const size_t n = ctx->scene.n_geoms;
     *out_n = n;
     if (n > capacity) return fail(ctx, FORMA_E_CAPACITY, "layer table capacity too small");
     if (n == 0) return FORMA_OK;
@@ -1586,10 +1554,10 @@ int forma_hip_set_styles(forma_hip_ctx* ctx, const uint32_t* style_offsets, size
     if ((rc = upload(ctx, ctx->layer_col, ctx->h_layer_col.data(), n_orders * 4))) return rc;
     if (unchanged && (rc = upload(ctx, ctx->unchanged, unchanged, n_orders))) return rc;
     HIPCHECK(hipStreamSynchronize(ctx->stream));
-    ctx->n_orders = n_orders; ctx->n_words = n_words; ctx->scene_has_clips = clips; ctx->scene_simple = simple;
-    ctx->costly_layers = costly;
-    ctx->have_unchanged = unchanged != nullptr;
-    ctx->any_texture = any_texture; ctx->max_image_index = max_image;
+    ctx->scene.n_orders = n_orders; ctx->scene.n_words = n_words; ctx->scene.scene_has_clips = clips; ctx->scene.scene_simple = simple;
+    ctx->scene.costly_layers = costly;
+    ctx->scene.have_unchanged = unchanged != nullptr;
+    ctx->scene.any_texture = any_texture; ctx->scene.max_image_index = max_image;
     share_scene(ctx);
     return FORMA_OK;
 }
@@ -1607,7 +1575,7 @@ int forma_hip_set_images(forma_hip_ctx* ctx, const forma_image_t* images, size_t
     if ((rc = upload(ctx, ctx->images, images, n_images))) return rc;
     if ((rc = upload(ctx, ctx->texels, texels, n_texels * 4))) return rc;
     HIPCHECK(hipStreamSynchronize(ctx->stream));
-    ctx->n_images = n_images;
+    ctx->scene.n_images = n_images;
     share_scene(ctx);
     return FORMA_OK;
 }
@@ -1659,15 +1627,6 @@ int forma_hip_flatten(forma_hip_ctx* ctx, const forma_flatten_tables_t* t, float
 
 // ---- the geometry store as an incremental store ------------------------------------------------------------
 namespace {
-// the context's page-locked staging buffer (one append's work items, one retain's tables): grown geometrically, kept
-int geo_staging(forma_hip_ctx* ctx, size_t bytes) {
-    if (bytes <= ctx->h_geo_cap && ctx->h_geo) return FORMA_OK;
-    const size_t want = std::max<size_t>(std::max(bytes, ctx->h_geo_cap + ctx->h_geo_cap / 2), 4096);
-    if (ctx->h_geo) { (void)hipHostFree(ctx->h_geo); ctx->h_geo = nullptr; ctx->h_geo_cap = 0; }
-    HIPCHECK(hipHostMalloc((void**)&ctx->h_geo, want, hipHostMallocDefault));
-    ctx->h_geo_cap = want;
-    return FORMA_OK;
-}
 // an edit of the store, seen from the frame path: the line count and everything provisioned from it follow n_points at the
 // next frame (run_rasterize_frame, run_line_table); the predictions stay — N, J and the row / slice shapes are bounds a
 // read-back-free frame is checked against on the device (k_runs_count, k_frame_tail: plan_bad, N <= bN, J <= bJ), the key
@@ -1675,13 +1634,13 @@ int geo_staging(forma_hip_ctx* ctx, size_t bytes) {
 // measured slice length are hints — exactly what forma_hip_set_geoms relies on when a transform moves every line.  What cannot
 // stay is a fused frame's unsorted stream, which restore_unsorted would rebuild from the lines as they are NOW.
 void geometry_edited(forma_hip_ctx* ctx) {
-    if (ctx->seg_u_fused) { ctx->seg_u_fused = false; ctx->have_unsorted = false; }
-    for (forma_hip_ctx* sl : ctx->slots) if (sl->seg_u_fused) { sl->seg_u_fused = false; sl->have_unsorted = false; }
-    // (the bucket frames of the exchange layout size their buckets from the last local count: those plan anew, like the
-    //  multi-device context above them)
-    ctx->xpred_valid = false;
-    for (forma_hip_ctx* sl : ctx->slots) sl->xpred_valid = false;
-    ctx->cnt.geometry_points = ctx->n_points;
+    for (forma_hip_ctx* sl : frame_slots(ctx)) {
+        if (sl->seg_u_fused) { sl->seg_u_fused = false; sl->have_unsorted = false; }
+        // (the bucket frames of the exchange layout size their buckets from the last local count: those plan anew, like the
+        //  multi-device context above them)
+        sl->learned.store_edited();
+    }
+    ctx->cnt.geometry_points = ctx->scene.n_points;
     share_scene(ctx);
 }
 }  // namespace
@@ -1705,7 +1664,7 @@ int forma_hip_geometry_append(forma_hip_ctx* ctx, const forma_flatten_tables_t* 
           end = affines[i].first + affines[i].count;
       } }
     if (ctx->multi) return multi_geometry_append(ctx, t, line_slot, affines, n_affines);
-    if (ctx->n_points + np >= (1ull << 30)) return fail(ctx, FORMA_E_ARG, "too many points");
+    if (ctx->scene.n_points + np >= (1ull << 30)) return fail(ctx, FORMA_E_ARG, "too many points");
     HIPCHECK(hipSetDevice(ctx->device));
     int rc;
     if ((rc = scene_drain(ctx))) return rc;               // frames in flight still read the store (and it may move when it grows)
@@ -1713,9 +1672,9 @@ int forma_hip_geometry_append(forma_hip_ctx* ctx, const forma_flatten_tables_t* 
     // spline, 8 per affine range
     const size_t words = 4 * np + (9 + 7) * nq + 4 * ns + 8 * n_affines;
     const size_t bytes = words * 4;
-    if ((rc = geo_staging(ctx, bytes))) return rc;
+    HIPCHECK(ctx->h_geo.ensure(bytes, 4096, true));      // (one append's work items: grown geometrically, kept)
     HIPCHECK(ctx->geo_blob.ensure(bytes));
-    uint32_t* h = (uint32_t*)ctx->h_geo;
+    uint32_t* h = ctx->h_geo.as<uint32_t>();
     const uint32_t* d = ctx->geo_blob.as<uint32_t>();
     forma_flatten_tables_t dt = *t;
     size_t at = 0;
@@ -1740,7 +1699,7 @@ int forma_hip_geometry_append(forma_hip_ctx* ctx, const forma_flatten_tables_t* 
         at += 8;
     }
     // the store grows geometrically and keeps its contents
-    const size_t n_old = ctx->n_points, n_new = n_old + np;
+    const size_t n_old = ctx->scene.n_points, n_new = n_old + np;
     HIPCHECK(ctx->x.grow_keep(n_new * 4, n_old * 4, ctx->stream));
     HIPCHECK(ctx->y.grow_keep(n_new * 4, n_old * 4, ctx->stream));
     HIPCHECK(ctx->line_slot.grow_keep(n_new * 4, n_old * 4, ctx->stream));
@@ -1749,7 +1708,7 @@ int forma_hip_geometry_append(forma_hip_ctx* ctx, const forma_flatten_tables_t* 
     launch_flatten_store(ctx->stream, &dt, A);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(ctx->stream));          // (the staging buffer is free again; the frame slots' streams see the points)
-    ctx->n_points = n_new;
+    ctx->scene.n_points = n_new;
     ctx->cnt.geometry_appends++; ctx->cnt.geometry_bytes_h2d += bytes;
     geometry_edited(ctx);
     return FORMA_OK;
@@ -1766,14 +1725,14 @@ int forma_hip_geometry_retain(forma_hip_ctx* ctx, const forma_keep_range_t* keep
     uint64_t end = 0, n_out = 0;
     size_t n_live = 0;
     for (size_t i = 0; i < n_keep; i++) {
-        if (keep[i].first < end || keep[i].count > ctx->n_points || keep[i].first > ctx->n_points - keep[i].count)
+        if (keep[i].first < end || keep[i].count > ctx->scene.n_points || keep[i].first > ctx->scene.n_points - keep[i].count)
             return fail(ctx, FORMA_E_ARG, "keep ranges must be ascending, disjoint and inside the store");
         end = keep[i].first + keep[i].count;
         n_out += keep[i].count; n_live += keep[i].count ? 1 : 0;
     }
     const size_t bytes = (3 * n_live + n_slots) * 4;
-    if ((rc = geo_staging(ctx, std::max<size_t>(bytes, 4)))) return rc;
-    uint32_t* h = (uint32_t*)ctx->h_geo;
+    HIPCHECK(ctx->h_geo.ensure(bytes, 4096, true));      // (one retain's tables)
+    uint32_t* h = ctx->h_geo.as<uint32_t>();
     { uint32_t dst = 0; size_t k = 0;
       for (size_t i = 0; i < n_keep; i++) {
           if (!keep[i].count) continue;
@@ -1797,7 +1756,7 @@ int forma_hip_geometry_retain(forma_hip_ctx* ctx, const forma_keep_range_t* keep
         if (h[0]) return fail(ctx, FORMA_E_ARG, "the store holds a slot beyond the remap table");   // (nothing was swapped: the store is as it was)
         std::swap(ctx->x, ctx->x_spare); std::swap(ctx->y, ctx->y_spare); std::swap(ctx->line_slot, ctx->line_slot_spare);
     }
-    ctx->n_points = (size_t)n_out;
+    ctx->scene.n_points = (size_t)n_out;
     ctx->cnt.geometry_retains++; ctx->cnt.geometry_bytes_h2d += bytes;
     geometry_edited(ctx);
     return FORMA_OK;
@@ -1806,7 +1765,7 @@ int forma_hip_geometry_retain(forma_hip_ctx* ctx, const forma_keep_range_t* keep
 int forma_hip_read_geometry(forma_hip_ctx* ctx, float* x, float* y, uint32_t* line_slot, size_t capacity_points, size_t* out_points) {
     if (!ctx || !out_points) return fail(ctx, FORMA_E_ARG, "null out_points");
     if (ctx->multi) ctx = multi_first(ctx);
-    const size_t n = ctx->n_points;
+    const size_t n = ctx->scene.n_points;
     *out_points = n;
     if (n > capacity_points) return fail(ctx, FORMA_E_CAPACITY, "geometry capacity too small");
     if (n == 0) return FORMA_OK;
@@ -1823,7 +1782,7 @@ int forma_hip_read_geometry(forma_hip_ctx* ctx, float* x, float* y, uint32_t* li
 int forma_hip_counters(forma_hip_ctx* ctx, forma_counters_t* out) {
     if (!ctx || !out) return FORMA_E_ARG;
     if (ctx->multi) return multi_counters(ctx, out);
-    ctx->cnt.geometry_points = ctx->n_points;
+    ctx->cnt.geometry_points = ctx->scene.n_points;
     *out = ctx->cnt;
     return FORMA_OK;
 }
@@ -1834,7 +1793,7 @@ int forma_hip_prepare_lines(forma_hip_ctx* ctx, uint32_t width, uint32_t height,
     if (!ctx) return FORMA_E_ARG;
     ENTER_STAGE(ctx);
     HIPCHECK(hipSetDevice(ctx->device));
-    const size_t n = ctx->n_points ? ctx->n_points - 1 : 0;
+    const size_t n = ctx->scene.n_points ? ctx->scene.n_points - 1 : 0;
     if (n && (!orders || !x0 || !y0 || !dx || !dy || !a || !b || !c || !d || !lengths)) return fail(ctx, FORMA_E_ARG, "null output");
     ctx->n_lines = n;
     if (n == 0) return FORMA_OK;
@@ -1844,7 +1803,7 @@ int forma_hip_prepare_lines(forma_hip_ctx* ctx, uint32_t width, uint32_t height,
     for (DevBuf* bb : lb) HIPCHECK(bb->ensure(n * 4));
     HIPCHECK(ctx->scan_tmp.ensure(scan_tmp_words(std::max<size_t>(n, 1 << 16)) * 4));
     launch_prepare_lines(ctx->stream, ctx->x.as<float>(), ctx->y.as<float>(), ctx->line_slot.as<uint32_t>(), (uint32_t)n,
-                         ctx->geoms.as<forma_geom_t>(), (uint32_t)ctx->n_geoms, (float)width, (float)height, -3.0e38f, 3.0e38f,
+                         ctx->geoms.as<forma_geom_t>(), (uint32_t)ctx->scene.n_geoms, (float)width, (float)height, -3.0e38f, 3.0e38f,
                          ctx->l_order.as<uint32_t>(), ctx->l_x0.as<float>(), ctx->l_y0.as<float>(), ctx->l_dx.as<float>(),
                          ctx->l_dy.as<float>(), ctx->l_a.as<float>(), ctx->l_b.as<float>(), ctx->l_c.as<float>(),
                          ctx->l_d.as<float>(), ctx->l_len.as<uint32_t>());
@@ -1981,7 +1940,7 @@ struct Front {
 // forma_hip_counters' frame counters live in the context the caller holds (a frame slot books on its owner)
 inline forma_counters_t& frame_counters(forma_hip_ctx* ctx, const Front& f) { return (ctx->owner && !f.received ? ctx->owner : ctx)->cnt; }
 
-inline bool may_enqueue(const forma_hip_ctx* ctx) { return ctx->pred_valid && ctx->pred_counts_valid && !ctx->no_async; }
+inline bool may_enqueue(const forma_hip_ctx* ctx) { return ctx->learned.pred_valid && ctx->learned.pred_counts_valid && !ctx->dbg.sync; }
 
 // The front of the context's own geometry, read-back-free: N, J and the sort plan are predicted from the previous frame (bounds
 // with slack); device-side guards keep a wrong guess memory-safe.
@@ -2003,7 +1962,7 @@ int enqueue_own_kernels(forma_hip_ctx* ctx, const PaintArgs& a, bool timing, uin
 }
 int enqueue_own(forma_hip_ctx* ctx, FrameRequest& r, bool* parked) {
     const PaintArgs a = r.paint();
-    r.bN = ctx->pred_N + ctx->pred_N / 16 + 4096; r.bJ = ctx->pred_J + ctx->pred_J / 16 + 4096;
+    r.bN = ctx->learned.pred_N + ctx->learned.pred_N / 16 + 4096; r.bJ = ctx->learned.pred_J + ctx->learned.pred_J / 16 + 4096;
     ctx->split_want = !parked && r.dst && !r.timing();    // (into caller memory and verified at once: the painter may run in bands, run_paint)
     ctx->split_n = 0;
     ctx->frame_has_dst = parked && r.dst;                 // (sort_workgroups: such a frame's digit passes keep the whole chip)
@@ -2053,20 +2012,20 @@ int wait_frame_tail(forma_hip_ctx* ctx, bool timing) {
 // a verified frame's painters left their heaviest-first lists: they become the current set, and the threshold is steered
 void take_over_order(forma_hip_ctx* ctx) {
     if (ctx->order_pending < 0) return;
-    ctx->order_cur = ctx->order_pending; ctx->order_sig = ctx->order_pending_sig; ctx->order_pending = -1;
+    ctx->learned.order_cur = ctx->order_pending; ctx->learned.order_sig = ctx->order_pending_sig; ctx->order_pending = -1;
     // steer the threshold: the heavy section should hold the few percent of the tiles that make the launch's tail
     const uint32_t nh = ctx->h_info->n_heavy, nt = std::max(ctx->order_tiles, 1u);
-    if (nh * 16u > nt) ctx->order_thr = std::min<uint32_t>(ctx->order_thr + ctx->order_thr / 4u, 1u << 24);        // > 6 %
-    else if (nh * 50u < nt) ctx->order_thr = std::max<uint32_t>(ctx->order_thr - ctx->order_thr / 5u, 1u << 12);     // < 2 %
+    if (nh * 16u > nt) ctx->learned.order_thr = std::min<uint32_t>(ctx->learned.order_thr + ctx->learned.order_thr / 4u, 1u << 24);        // > 6 %
+    else if (nh * 50u < nt) ctx->learned.order_thr = std::max<uint32_t>(ctx->learned.order_thr - ctx->learned.order_thr / 5u, 1u << 12);     // < 2 %
     // ... of a scene that HAS a tail: a tile is heavy from twice the average on (sampled: FrameInfo::cost_*)
     if (!ctx->h_info->cost_n) return;
     const uint64_t mean = ((uint64_t)ctx->h_info->cost_sum << 8) / ctx->h_info->cost_n;
-    ctx->order_thr = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(ctx->order_thr, 2 * mean), 1u << 24);
+    ctx->learned.order_thr = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(ctx->learned.order_thr, 2 * mean), 1u << 24);
     // a FLAT scene (the 8K triangle scene: 262 144 tiles of ~21 k clocks, none beyond twice that) has no tail to hide, and
     // the bookkeeping of the order — a flag byte per tile, the empty heavy section — costs its painter 10 %: three such
     // frames in a row switch the order off for the next 256
-    if (ctx->order_thr <= 2 * mean && nh * 100u < nt) { if (++ctx->order_flat >= 3) { ctx->order_off = 256; ctx->order_flat = 0; ctx->order_cur = -1; } }
-    else ctx->order_flat = 0;
+    if (ctx->learned.order_thr <= 2 * mean && nh * 100u < nt) { if (++ctx->learned.order_flat >= 3) { ctx->learned.order_off = 256; ctx->learned.order_flat = 0; ctx->learned.order_cur = -1; } }
+    else ctx->learned.order_flat = 0;
 }
 
 // The verdict on a read-back-free frame whose FrameInfo has arrived.  FORMA_OK: its predictions held and are taken over.
@@ -2081,17 +2040,17 @@ int judge_frame(forma_hip_ctx* ctx, const FrameRequest& r, bool own_counts) {
     ctx->n_seg = N; ctx->last_runs = J;
     if (own_counts) ctx->n_compact = fi.n_compact;
     if (!fi.plan_bad && J <= r.bJ && (!own_counts || N <= r.bN)) {
-        if (own_counts) { take_over_order(ctx); ctx->pred_N = N; }
-        ctx->pred_J = J; ctx->pred_max_row = fi.max_row_runs;
-        if (ctx->bias_banned) ctx->bias_banned--;
+        if (own_counts) { take_over_order(ctx); ctx->learned.pred_N = N; }
+        ctx->learned.pred_J = J; ctx->learned.pred_max_row = fi.max_row_runs;
+        if (ctx->learned.bias_banned) ctx->learned.bias_banned--;
         return FORMA_OK;
     }
     if (own_counts) { const int src = settle_split(ctx); if (src) return src; }
-    if (ctx->small_tried && fi.plan_bad) ctx->small_banned = true;   // (one cause of plan_bad: a slice beyond the small variant)
-    if (ctx->covl_tried && fi.plan_bad) ctx->covl_banned = true;     // (another: a row beyond the COVL carry variant's LDS)
+    if (ctx->small_tried && fi.plan_bad) ctx->learned.small_banned = true;   // (one cause of plan_bad: a slice beyond the small variant)
+    if (ctx->covl_tried && fi.plan_bad) ctx->learned.covl_banned = true;     // (another: a row beyond the COVL carry variant's LDS)
     if (ctx->plan_biased && fi.plan_bad) ban_bias(ctx);              // (another: a key outside the span the digits were planned for)
-    ctx->pred_counts_valid = false;
-    if (own_counts) { ctx->order_cur = -1; ctx->order_pending = -1; }
+    ctx->learned.pred_counts_valid = false;
+    if (own_counts) { ctx->learned.order_cur = -1; ctx->order_pending = -1; }
     clear_stage_flags(ctx);
     return FORMA_RETRY;
 }
@@ -2122,8 +2081,8 @@ int run_sync(forma_hip_ctx* ctx, const FrameRequest& r, const Front& f) {
         rc = run_paint(ctx, DevCount{nullptr, (uint32_t)ctx->n_seg}, r.paint(), r.timing());
         if (rc == FORMA_RETRY) { clear_stage_flags(ctx); continue; }
         if (rc || (rc = deliver(ctx, r, false, false))) return rc;
-        if (!f.received) ctx->pred_N = (uint32_t)ctx->n_seg;
-        ctx->pred_J = ctx->last_runs; ctx->pred_counts_valid = true;
+        if (!f.received) ctx->learned.pred_N = (uint32_t)ctx->n_seg;
+        ctx->learned.pred_J = ctx->last_runs; ctx->learned.pred_counts_valid = true;
         return FORMA_OK;
     }
     return fail(ctx, FORMA_E_INTERNAL, "sort plan did not converge");
@@ -2147,7 +2106,7 @@ int start_frame(forma_hip_ctx* ctx, FrameRequest& r, const Front& f, bool* parke
 int render_on(forma_hip_ctx* ctx, FrameRequest& r, bool* parked) {
     clear_stage_flags(ctx);
     { const int rc = tables_catch_up(ctx); if (rc) return rc; }        // layer-table edits travel with the frame, on its stream
-    if (r.width != ctx->pred_w || r.height != ctx->pred_h) { ctx->pred_counts_valid = false; ctx->pred_w = r.width; ctx->pred_h = r.height; }
+    ctx->learned.own_canvas(r.width, r.height);
     return start_frame(ctx, r, OWN_GEOMETRY, parked);
 }
 
@@ -2183,19 +2142,13 @@ void share_scene(forma_hip_ctx* o) {
         const std::vector<DevBuf*> mine = sl->scene_bufs(), theirs = o->scene_bufs();
         for (size_t i = 0; i < mine.size(); i++) mine[i]->borrow(*theirs[i]);
         if (o->tab_on && sl->geoms_own.p) sl->geoms.borrow(sl->geoms_own);   // (layer-table edits: the slot's own table)
-        sl->n_points = o->n_points; sl->n_geoms = o->n_geoms; sl->n_orders = o->n_orders; sl->n_words = o->n_words; sl->n_images = o->n_images;
-        sl->max_geom_order = o->tab_on ? o->tab_max_order : o->max_geom_order;   // (edits in use: the table's, which the slot holds or takes before its next frame)
-        sl->max_image_index = o->max_image_index; sl->any_texture = o->any_texture;
-        sl->scene_has_clips = o->scene_has_clips; sl->scene_simple = o->scene_simple; sl->costly_layers = o->costly_layers; sl->have_unchanged = o->have_unchanged;
-        sl->band_row0 = o->band_row0; sl->band_row1 = o->band_row1;
-        sl->line_ranged = o->line_ranged; sl->line_lo = o->line_lo; sl->line_hi = o->line_hi;
+        sl->scene = o->scene;
+        if (o->tab_on) sl->scene.max_geom_order = o->tab_max_order;   // (edits in use: the table's, which the slot holds or takes before its next frame)
     }
 }
 void invalidate_counts(forma_hip_ctx* o) {                 // new geometry / band: every slot re-learns N and J synchronously
-    for (size_t i = 0; i < std::max<size_t>(o->slots.size(), 1); i++) {
-        forma_hip_ctx* c = o->slots.empty() ? o : o->slots[i];             // (the owner is slots[0] whenever there are slots)
-        c->pred_counts_valid = false; c->xpred_valid = false; c->small_banned = false; c->covl_banned = false; c->bias_banned = 0; c->bias_ban_len = 0; c->pred_range.valid = false;
-        c->order_off = 0; c->order_flat = 0; c->order_cur = -1; c->cull_on = false; c->pred_slice_len = 0;
+    for (forma_hip_ctx* c : frame_slots(o)) {
+        c->learned.new_geometry();
         // a fused frame's unsorted stream is rebuilt from the scene's CURRENT lines and band (restore_unsorted): gone with them
         if (c->seg_u_fused) { c->seg_u_fused = false; c->have_unsorted = false; }
     }
@@ -2333,7 +2286,7 @@ int forma_hip_set_frames_in_flight(forma_hip_ctx* ctx, int n) {
         forma_hip_ctx* sl = nullptr;
         if ((rc = forma_hip_create(&sl, ctx->device))) return fail(ctx, rc, "frames in flight: cannot create a frame slot");
         sl->owner = ctx;
-        sl->digit_bits = ctx->digit_bits; sl->no_async = ctx->no_async; sl->global_runsort = ctx->global_runsort;
+        sl->dbg = ctx->dbg;                               // (a slot's switches are its owner's, not the environment's as it stands now)
         ctx->slots.push_back(sl);
     }
     if (ctx->slots.size() == 1) ctx->slots.clear();
@@ -2405,12 +2358,10 @@ int forma_hip_trim(forma_hip_ctx* ctx) {
     if (!ctx) return FORMA_E_ARG;
     if (ctx->multi) return multi_trim(ctx);
     { const int rc = fd_drain(ctx); if (rc) return rc; }
-    std::vector<forma_hip_ctx*> all{ctx};
-    for (forma_hip_ctx* sl : ctx->slots) if (sl != ctx) all.push_back(sl);
-    for (forma_hip_ctx* c : all) {
+    for (forma_hip_ctx* c : frame_slots(ctx)) {
         HIPCHECK(hipSetDevice(c->device));
         HIPCHECK(hipStreamSynchronize(c->stream));
-        c->order_cur = -1; c->order_pending = -1; c->order_cnt_dev = nullptr; c->order_keep_dev = nullptr;
+        c->learned.order_cur = -1; c->order_pending = -1; c->order_cnt_dev = nullptr; c->order_keep_dev = nullptr;
         size_t freed = 0;
         for (const auto& bufs : {c->frame_bufs(), c->trimmed_bufs()})
             for (DevBuf* b : bufs) { if (!b->borrowed) freed += b->cap; b->release(); }
@@ -2421,7 +2372,7 @@ int forma_hip_trim(forma_hip_ctx* ctx) {
             for (auto& tcache : c->caches) kept += tcache.tiles.cap + tcache.image.cap;
             fprintf(stderr, "[forma_hip_trim] context %p: released %zu bytes, keeps %zu\n", (void*)c, freed, kept);
         }
-        if (c->h_stage) { (void)hipHostFree(c->h_stage); c->h_stage = nullptr; c->h_stage_cap = 0; }   // (pinned: a whole 4K image after a cache frame)
+        c->h_stage.release();                             // (pinned: a whole 4K image after a cache frame)
         c->sorted = nullptr; c->n_seg = 0; c->have_unsorted = false;
         c->cur_image = nullptr; c->img_w = 0; c->img_h = 0;
         c->pending_masks = PendingMasks{nullptr, 0u};
@@ -2497,7 +2448,7 @@ int restore_unsorted(forma_hip_ctx* ctx) {
     const LineSource S = geometry_source(ctx, ctx->fused_w, ctx->fused_h);
     launch_rasterize(ctx->stream, S, DevCount{nullptr, ctx->h_info->n_compact}, DevCount{nullptr, (uint32_t)ctx->n_seg},
                      ctx->cl_idx.as<uint32_t>(), ctx->cl_start.as<uint32_t>(), ctx->block_first.as<uint32_t>(), ctx->seg_u.as<uint64_t>(),
-                     ctx->info.as<FrameInfo>(), (int)ctx->band_row0, (int)ctx->band_row1, ctx->ras_masks.as<uint32_t>(), /*reduce_now=*/false, nullptr);
+                     ctx->info.as<FrameInfo>(), (int)ctx->scene.band_row0, (int)ctx->scene.band_row1, ctx->ras_masks.as<uint32_t>(), /*reduce_now=*/false, nullptr);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(ctx->stream));
     ctx->seg_u_fused = false;
@@ -2526,20 +2477,15 @@ int fd_tiles_written(forma_hip_ctx* ctx, uint8_t* flags, size_t n_tiles) {
     memset(flags, 0, n_tiles);
     if (ctx->lw_cache && !ctx->lw_flags_on_host) {        // device-resident frame (dst == NULL): fetch the flags now
         HIPCHECK(hipSetDevice(ctx->device));
-        if (ctx->h_written_cap < T) {
-            if (ctx->h_written) (void)hipHostFree(ctx->h_written);
-            ctx->h_written = nullptr; ctx->h_written_cap = 0;
-            HIPCHECK(hipHostMalloc((void**)&ctx->h_written, T, hipHostMallocDefault));
-            ctx->h_written_cap = T;
-        }
-        HIPCHECK(hipMemcpyAsync(ctx->h_written, ctx->cache_written.p, T, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHECK(ctx->h_written.ensure(T));
+        HIPCHECK(hipMemcpyAsync(ctx->h_written.p, ctx->cache_written.p, T, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHECK(hipStreamSynchronize(ctx->stream));
         ctx->lw_flags_on_host = true;
     }
     for (uint32_t ty = ctx->lw_ty0; ty < ctx->lw_ty1; ty++)
         for (uint32_t tx = ctx->lw_tx0; tx < ctx->lw_tx1; tx++) {
             const size_t t = (size_t)ty * ctx->lw_tiles_w + tx;
-            flags[t] = ctx->lw_cache ? (ctx->h_written[t] ? 1 : 0) : 1;
+            flags[t] = ctx->lw_cache ? (ctx->h_written.as<uint8_t>()[t] ? 1 : 0) : 1;
         }
     return FORMA_OK;
 }
@@ -2550,7 +2496,7 @@ extern "C" {
 int forma_hip_set_band(forma_hip_ctx* ctx, uint32_t row0, uint32_t row1) {
     ENTER_SINGLE(ctx);
     if (row1 != 0 && row0 >= row1) return fail(ctx, FORMA_E_ARG, "empty band");
-    ctx->band_row0 = row1 ? row0 : 0; ctx->band_row1 = row1;
+    ctx->scene.band_row0 = row1 ? row0 : 0; ctx->scene.band_row1 = row1;
     invalidate_counts(ctx);
     share_scene(ctx);
     return FORMA_OK;
@@ -2641,7 +2587,7 @@ int forma_hip_exchange_plan(forma_hip_ctx* ctx, const uint32_t* row_edges, uint3
     HIPCHECK(hipMemsetAsync(ctx->xrecv.p, 0, (words + SEG_PAD) * 8, ctx->stream));
     HIPCHECK(hipStreamSynchronize(ctx->stream));
     ctx->xplanned = true;
-    ctx->pred_valid = false; ctx->pred_counts_valid = false; ctx->xpred_valid = false;
+    ctx->learned.new_exchange_plan();
     return FORMA_OK;
 }
 
@@ -2666,13 +2612,13 @@ int forma_hip_rasterize_bucket_frame(forma_hip_ctx* ctx, uint32_t width, uint32_
     // whose true count exceeds the bound is flagged by k_owner_scan to every receiver (FORMA_E_CAPACITY -> the host re-plans).
     // The true count of every bucket frame is copied to a pinned word on the stream; the owner's half of the frame ends in a
     // stream synchronisation, so by the next bucket frame it has landed and refreshes the prediction (an animation drifts).
-    if (width != ctx->xpred_w || height != ctx->xpred_h) { ctx->xpred_valid = false; ctx->xpred_w = width; ctx->xpred_h = height; }
-    if (ctx->xpred_valid && ctx->h_xlocal[1]) {
+    ctx->learned.bucket_canvas(width, height);
+    if (ctx->learned.xpred_valid && ctx->h_xlocal[1]) {
         HIPCHECK(hipStreamSynchronize(ctx->stream));      // (a no-op after forma_hip_gather_sort_paint_frame)
-        ctx->xpred_N = ctx->h_xlocal[0];
+        ctx->learned.xpred_N = ctx->h_xlocal[0];
     }
     ctx->h_xlocal[1] = 0;
-    const uint32_t bN = (ctx->xpred_valid && !ctx->no_async) ? ctx->xpred_N + ctx->xpred_N / 16 + 4096 : 0;
+    const uint32_t bN = (ctx->learned.xpred_valid && !ctx->dbg.sync) ? ctx->learned.xpred_N + ctx->learned.xpred_N / 16 + 4096 : 0;
     if ((rc = poison_frame_buffers(ctx))) return rc;
     // read-back-free on both halves: this call's first kernel also clears what the owner's half of the frame
     // (forma_hip_gather_sort_paint_frame: sort scratch, tile tables, run chain for a band of n_ranks x capacity segments) expects
@@ -2682,7 +2628,7 @@ int forma_hip_rasterize_bucket_frame(forma_hip_ctx* ctx, uint32_t width, uint32_
     if ((rc = run_rasterize_frame(ctx, width, height, timing, false, bN, ahead ? &Z : nullptr, ahead ? &cleared : nullptr))) return rc;
     FrameInfo* dinfo = ctx->info.as<FrameInfo>();
     DevCount nc = bN ? DevCount{&dinfo->n_segments, bN} : DevCount{nullptr, (uint32_t)ctx->n_seg};
-    if (!bN) { ctx->xpred_N = (uint32_t)ctx->n_seg; ctx->xpred_valid = true; }
+    if (!bN) { ctx->learned.xpred_N = (uint32_t)ctx->n_seg; ctx->learned.xpred_valid = true; }
     HIPCHECK(ctx->seg_u.ensure(((size_t)std::max<uint32_t>(nc.bound, 1) + SEG_PAD) * 8));
     HIPCHECK(ctx->xscratch.ensure(owner_scratch_words(std::max<size_t>(nc.bound, 1)) * 4));
     stage_begin(ctx, ST_XCHG, timing);
@@ -2727,14 +2673,14 @@ int enqueue_received(forma_hip_ctx* ctx, FrameRequest& r, bool* parked) {
     const uint64_t* recv = self ? ctx->xsend.as<uint64_t>() : ctx->xrecv.as<uint64_t>();
     FrameInfo* dinfo = ctx->info.as<FrameInfo>();
     int rc;
-    r.bJ = ctx->pred_J + ctx->pred_J / 16 + 4096;
-    ctx->live44 = ctx->pred_live44; ctx->layer_sorted = ctx->pred_layer_sorted; ctx->speculated = true;
+    r.bJ = ctx->learned.pred_J + ctx->learned.pred_J / 16 + 4096;
+    ctx->live44 = ctx->learned.pred_live44; ctx->layer_sorted = ctx->learned.pred_layer_sorted; ctx->speculated = true;
     uint64_t live = ctx->live44;
     if (ctx->layer_sorted) live &= ~0x1FFFFFull;
     // The received buckets are sorted where they lie: the histogram kernel and the first digit pass read the rank-major
     // concatenation through a logical -> physical index map, so nothing is gathered (k_gather_chunks: one more read and
     // write of the whole band).  Needs at least one digit pass; FORMA_HIP_DEBUG=xgather keeps the gather (A/B, tests).
-    if (!ctx->xgather_always && live != 0 && bound > 1) {
+    if (!ctx->dbg.xgather && live != 0 && bound > 1) {
         if ((rc = reset_info(ctx))) return rc;
         ctx->have_unsorted = false; ctx->n_lines = 0;
         const ChunkedSrc C{recv, G, ctx->xcap, ctx->xmask.as<uint32_t>()};
@@ -2832,7 +2778,7 @@ int fd_set_line_range(forma_hip_ctx* ctx, bool ranged, size_t lo, size_t hi) {
     if (ranged && lo > hi) return fail(ctx, FORMA_E_ARG, "line range");
     int rc = fd_drain(ctx);
     if (rc) return rc;
-    ctx->line_ranged = ranged; ctx->line_lo = ranged ? lo : 0; ctx->line_hi = ranged ? hi : 0;
+    ctx->scene.line_ranged = ranged; ctx->scene.line_lo = ranged ? lo : 0; ctx->scene.line_hi = ranged ? hi : 0;
     invalidate_counts(ctx);
     share_scene(ctx);
     return FORMA_OK;
@@ -2843,18 +2789,18 @@ int fd_line_sums(forma_hip_ctx* ctx, uint32_t width, uint32_t height, std::vecto
     int rc = fd_drain(ctx);
     if (rc) return rc;
     HIPCHECK(hipSetDevice(ctx->device));
-    const size_t n = ctx->n_points ? ctx->n_points - 1 : 0;
+    const size_t n = ctx->scene.n_points ? ctx->scene.n_points - 1 : 0;
     sums.assign(n, 0u);
     if (n == 0) return FORMA_OK;
     // per-line lengths of ALL lines (the frame path's count kernel, segment.rs:298-383 restated in k_line_len), then the scan
     HIPCHECK(ctx->l_len.ensure(n * 4));
     HIPCHECK(ctx->prep_scratch.ensure(prepare_scratch_words(n) * 4));
     HIPCHECK(ctx->scan_tmp.ensure(scan_tmp_words(std::max<size_t>(n, 1 << 16)) * 4));
-    const bool keep = ctx->line_ranged;
-    const uint32_t keep_b0 = ctx->band_row0, keep_b1 = ctx->band_row1;     // (ALL lines, whole canvas: neither a line share nor a band)
-    ctx->line_ranged = false; ctx->band_row0 = 0; ctx->band_row1 = 0;
+    const bool keep = ctx->scene.line_ranged;
+    const uint32_t keep_b0 = ctx->scene.band_row0, keep_b1 = ctx->scene.band_row1;     // (ALL lines, whole canvas: neither a line share nor a band)
+    ctx->scene.line_ranged = false; ctx->scene.band_row0 = 0; ctx->scene.band_row1 = 0;
     const LineSource S = geometry_source(ctx, width, height);
-    ctx->line_ranged = keep; ctx->band_row0 = keep_b0; ctx->band_row1 = keep_b1;
+    ctx->scene.line_ranged = keep; ctx->scene.band_row0 = keep_b0; ctx->scene.band_row1 = keep_b1;
     launch_line_lengths(ctx->stream, S, (uint32_t)n, ctx->l_len.as<uint32_t>(), ctx->prep_scratch.as<uint32_t>());
     launch_inclusive_scan_u32(ctx->stream, ctx->l_len.as<uint32_t>(), n, ctx->scan_tmp.as<uint32_t>(), nullptr);
     HIPCHECK(hipGetLastError());

@@ -56,6 +56,22 @@ struct DevBuf {
     template <class T> T* as() const { return (T*)p; }
 };
 
+// page-locked host memory that grows on demand and is kept: to exactly `bytes`, to at least `min_bytes`, or geometrically
+struct PinnedBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    hipError_t ensure(size_t bytes, size_t min_bytes = 0, bool geometric = false) {
+        if (bytes <= cap && p) return hipSuccess;
+        const size_t want = std::max(std::max(bytes, min_bytes), geometric ? cap + cap / 2 : 0);
+        release();
+        const hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
+        if (e == hipSuccess) cap = want; else p = nullptr;
+        return e;
+    }
+    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
+    template <class T> T* as() const { return (T*)p; }
+};
+
 constexpr uint32_t PAINT_WAVES_PER_CU = 24;     // wave slots of the general painter per CU (6 per SIMD): frames of at most n_cus x 24 painted
                                                 // tiles — every tile gets a slot at once — are painted by strips (api.cpp paint_by_strips)
 constexpr size_t SEG_PAD = 16;          // segment buffers are over-allocated: stream kernels read whole 64-byte lane pieces
@@ -98,6 +114,72 @@ struct FrameRequest {
     bool timing() const { return timings != nullptr; }
 };
 
+// What the uploaded scene IS, as far as the frame path needs scalars of it.  Written by the scene setters on the owner of the
+// frame slots; share_scene hands the whole struct to every slot with the borrowed buffers, so a fact added here reaches them all
+// (layer-table edits: a slot's n_geoms and max_geom_order then follow the table it holds, tables_catch_up).
+struct SceneFacts {
+    size_t n_points = 0, n_geoms = 0, n_orders = 0, n_words = 0, n_images = 0;
+    uint32_t max_geom_order = 0;            // largest order any geom slot names (FORMA_NONE slots aside)
+    uint32_t max_image_index = 0;           // largest image index a texture style names
+    bool any_texture = false;
+    bool scene_has_clips = false;
+    bool scene_simple = false;              // all layers solid + Over + unclipped: the painter's specialised kernel
+    size_t costly_layers = 0;               // layers with a gradient / texture fill, a blend mode other than Over, or clipped (strip painters: api.cpp)
+    bool have_unchanged = false;            // set_styles supplied per-order Layer::is_unchanged bytes
+    uint32_t band_row0 = 0, band_row1 = 0;  // band
+    // a sub-range [line_lo, line_hi) of the uploaded lines (line i joins points i and i + 1) when line_ranged.
+    // A multi-device context uploads the whole geometry to every device and gives each its share of the LINES (multi.cpp).
+    bool line_ranged = false;
+    size_t line_lo = 0, line_hi = 0;
+};
+
+// What verified frames taught a context (every frame slot learns for itself), and the events that un-teach it.  Read-back-free
+// frames are enqueued under these predictions and checked against them on the device; a synchronous frame re-learns them.
+struct Learned {
+    // sort-plan speculation: the varying-bit mask and the layer-sortedness of a scene rarely change between frames, so a frame
+    // plans its sort from the previous frame's values and verifies them when it is done (verify_speculation writes all three)
+    bool pred_valid = false, pred_layer_sorted = false;
+    uint64_t pred_live44 = 0;
+    // counts.  pred_N / pred_J: a frame's segments and runs (run_sync, judge_frame); pred_counts_valid: set by run_sync, dropped by
+    // judge_frame with a void frame; pred_w / pred_h: own_canvas.  xpred_*: the local count of the last bucket frame of the
+    // exchange layout and its canvas (forma_hip_rasterize_bucket_frame, bucket_canvas)
+    bool pred_counts_valid = false, xpred_valid = false;
+    uint32_t pred_N = 0, pred_J = 0, pred_w = 0, pred_h = 0;
+    uint32_t xpred_N = 0, xpred_w = 0, xpred_h = 0;
+    // shapes of the last verified frame
+    uint32_t pred_max_row = 0xFFFFFFFFu;    // most runs in one tile row (unknown: no local sort): judge_frame, replan_carry
+    uint32_t pred_row_spans = 0;            // spans per painted tile row: group lists pay above SPAN_GROUP_MIN_ROW (finish_frame)
+    uint32_t pred_slice_n = 0, pred_max_slice = 0;              // carry slices per tile row and the most runs in one (finish_frame)
+    bool pred_slice_small = false, pred_slice_half = false;     // ... under the small / the 512-lane carry kernel (finish_frame)
+    uint32_t pred_slice_len = 0;            // mean keys per (digit, block) slice of the last fused frame, 0: not measured (finish_frame)
+    bool pred_no_deep = false;              // it sent no tile to k_paint_deep (finish_frame)
+    KeyRange pred_range{0, 0, 0, 0, false}; // what its tile fields spanned (value-range digits, SortPlan::bias): finish_frame
+    // bans and probes
+    bool small_banned = false, covl_banned = false;   // a frame that guessed the small / the COVL carry variant was void (judge_frame)
+    uint32_t bias_banned = 0, bias_ban_len = 0;       // frames left of a ban on biased digits (judge_frame counts down) / length of the last one: re-armed
+                                                      // with back-off by ban_bias — an animated scene that left its span once gets the cheaper plan back
+    uint32_t fuse_skipped = 0;              // frames not fused since the slices were measured too short (fuse_first_digit, FUSE_PROBE)
+    // painter steering (PaintParams::order_*, ::cull)
+    struct OrderSig { uint32_t tiles_w = 0, tiles_h = 0, x0 = 0, x1 = 0, y0 = 0, y1 = 0;
+                      bool operator==(const OrderSig& o) const { return tiles_w == o.tiles_w && tiles_h == o.tiles_h && x0 == o.x0 && x1 == o.x1 && y0 == o.y0 && y1 == o.y1; } };
+    int order_cur = -1;                     // the set of order lists that is valid, -1: none (take_over_order; dropped by heavy_order, a void frame and trim)
+    OrderSig order_sig;                     // ... and the canvas / crop it was written for (take_over_order)
+    uint32_t order_flat = 0, order_off = 0; // frames in a row without a tail (take_over_order) / frames left with the order switched off (heavy_order counts down)
+    uint32_t order_thr = 1u << 16;          // shader clocks that make a tile heavy, steered per frame (take_over_order)
+    bool cull_on = false;                   // this geometry has had tiles beyond the wave painter's lists: occlusion culling is on (finish_frame)
+
+    // new geometry, band, line range or trim: the next frame re-learns N and J synchronously, bans and steering start over
+    void new_geometry() {
+        pred_counts_valid = false; xpred_valid = false; small_banned = false; covl_banned = false; bias_banned = 0; bias_ban_len = 0; pred_range.valid = false;
+        order_off = 0; order_flat = 0; order_cur = -1; cull_on = false; pred_slice_len = 0;
+    }
+    void store_edited() { xpred_valid = false; }            // (api.cpp geometry_edited says why the rest stays)
+    void new_exchange_plan() { pred_valid = false; pred_counts_valid = false; xpred_valid = false; }
+    // canvas changed: counts learned at another size predict nothing
+    void own_canvas(uint32_t w, uint32_t h) { if (w != pred_w || h != pred_h) { pred_counts_valid = false; pred_w = w; pred_h = h; } }
+    void bucket_canvas(uint32_t w, uint32_t h) { if (w != xpred_w || h != xpred_h) { xpred_valid = false; xpred_w = w; xpred_h = h; } }
+};
+
 struct forma_hip_ctx {
     int device = 0;
     uint32_t n_cus = 256;                   // hipDeviceProp_t::multiProcessorCount of `device` (MI355X: 256)
@@ -108,14 +190,13 @@ struct forma_hip_ctx {
     DevBuf x, y, line_slot, geoms, style_off, style_words, unchanged, images, texels;
     DevBuf layer_sf, layer_col;             // per order: style summary for the carry pre-pass (set_styles)
     std::vector<uint32_t> h_layer_sf, h_layer_col;
-    size_t n_points = 0, n_geoms = 0, n_orders = 0, n_words = 0, n_images = 0;
+    SceneFacts scene;
     // the geometry store as an incremental store (forma_hip_geometry_append / _retain): line_slot holds n_points entries on
     // the device, the last one FORMA_NONE (frames use n_points - 1 of them); retain compacts into the spare set and swaps
     DevBuf x_spare, y_spare, line_slot_spare;
     DevBuf geo_blob;                        // one append's work items / one retain's tables, as uploaded
     DevBuf geo_flag;                        // k_geom_retain: a stored slot beyond the remap table
-    uint8_t* h_geo = nullptr;               // pinned staging of geo_blob (grown geometrically, kept); its first word receives geo_flag
-    size_t h_geo_cap = 0;
+    PinnedBuf h_geo;                        // staging of geo_blob (grown geometrically, kept); its first word receives geo_flag
     // the layer table edited with frames in flight (forma_hip_update_geoms / _update_geoms_xf; api.cpp "layer-table edits").
     // The OWNER of the frame slots keeps the table on the host (h_tab: always, forma_hip_read_geoms answers from it) and, from
     // the first edit call on (tab_on), a journal of what changed at which sequence number; every slot then owns a table
@@ -133,44 +214,28 @@ struct forma_hip_ctx {
     DevBuf geoms_own;                       // every slot, the owner included: its table
     DevBuf geoms_shared;                    // owner: the table the slots shared before the first edit call (frames enqueued then still read it)
     DevBuf tab_blob;                        // every slot: one catch-up's records on the device
-    uint8_t* h_tab_stage = nullptr;         // every slot, pinned: the records / the whole table on their way (free again once the slot's frame is settled)
-    size_t h_tab_stage_cap = 0;
+    PinnedBuf h_tab_stage;                  // every slot: the records / the whole table on their way (free again once the slot's frame is settled)
     forma_counters_t cnt{};                 // forma_hip_counters (frame counters: kept by the owner of the frame slots)
-    uint32_t max_geom_order = 0;            // largest order any geom slot names (FORMA_NONE slots aside)
-    uint32_t max_image_index = 0;           // largest image index a texture style names
-    bool any_texture = false;
-    bool scene_has_clips = false;
     DevBuf run_lt;                  // one word per run: layer16 | open | tile_x + 1 (RunStyle, common.h)
     DevBuf rec_sp, run_lt_sp, row_sp;       // launch_runs' BLOCKS numbering (BlkRuns, common.h): records and digests indexed like the segments (N entries)
     DevBuf grp_tab, grp_list;       // span group lists (SpanGroups, common.h): table per (row, slice, group) and the entry pool
-    bool no_span_groups = false;    // FORMA_HIP_DEBUG=no_span_groups (A/B switch for tools/)
-    bool force_span_groups = false; // FORMA_HIP_DEBUG=span_groups: on every frame and for every row, however few spans (tests)
-    uint32_t pred_row_spans = 0;    // spans per painted tile row of the last verified frame: group lists pay above SPAN_GROUP_MIN_ROW
     uint32_t cur_rows_painted = 1;
-    bool scene_simple = false;      // all layers solid + Over + unclipped: the painter's specialised kernel
-    size_t costly_layers = 0;       // layers with a gradient / texture fill, a blend mode other than Over, or clipped (strip painters: api.cpp)
-    bool have_unchanged = false;            // set_styles supplied per-order Layer::is_unchanged bytes
     // lines
     DevBuf l_order, l_x0, l_y0, l_dx, l_dy, l_a, l_b, l_c, l_d, l_len, scan_tmp;   // parity entry points only
     DevBuf cl_idx, cl_start, block_first, prep_scratch;                              // frame path: compacted line table
-    bool pred_no_deep = false;              // the last verified frame sent no tile to k_paint_deep
     // carry pre-pass: slices per tile row and the LDS variant (api.cpp run_paint)
-    uint32_t cur_slices = 1, pred_slice_n = 0, pred_max_slice = 0, force_slices = 0;
+    uint32_t cur_slices = 1;
     // the painters' heaviest-first order (PaintParams::order_*): two sets of {counts, lists}; a read-back-free frame reads the set
     // the last verified frame of the same canvas / crop wrote and writes the other one
     DevBuf order_buf;
-    struct OrderSig { uint32_t tiles_w = 0, tiles_h = 0, x0 = 0, x1 = 0, y0 = 0, y1 = 0;
-                      bool operator==(const OrderSig& o) const { return tiles_w == o.tiles_w && tiles_h == o.tiles_h && x0 == o.x0 && x1 == o.x1 && y0 == o.y0 && y1 == o.y1; } };
-    OrderSig order_sig, order_pending_sig;
-    uint32_t order_flat = 0, order_off = 0;       // frames in a row without a tail / frames left with the order switched off
-    uint32_t order_thr = 1u << 16, order_tiles = 0;  // shader clocks that make a tile heavy (steered per frame), tiles of the pending frame
-    int order_cur = -1, order_pending = -1;       // set with valid lists (-1: none) / set this frame's painter writes (-1: none)
+    Learned::OrderSig order_pending_sig;
+    uint32_t order_tiles = 0;                     // tiles of the pending frame
+    int order_pending = -1;                       // set this frame's painter writes (-1: none)
     bool order_enable = false;                    // set by the caller of run_paint for frames that end with k_frame_tail
     const uint32_t* order_cnt_dev = nullptr; uint32_t* order_keep_dev = nullptr;   // what that k_frame_tail copies
-    bool cull_on = false;                         // this geometry has had tiles beyond the wave painter's lists: occlusion culling is on
-    bool cur_half = false, pred_slice_half = false;   // the 512-lane variant of the small carry kernel (api.cpp run_paint)
-    bool cur_small = false, pred_slice_small = false, small_tried = false, small_banned = false, no_small_carry = false;
-    bool covl_tried = false, covl_banned = false;   // the COVL carry variant (rows' covers in LDS) was this read-back-free frame's guess / a frame that guessed it was void
+    bool cur_half = false;                    // the 512-lane variant of the small carry kernel (api.cpp run_paint)
+    bool cur_small = false, small_tried = false;
+    bool covl_tried = false;                // the COVL carry variant (rows' covers in LDS) was this read-back-free frame's guess
     DevBuf slice_buf;                       // fused first digit pass (SliceSrc): slice table, tiles' first slices, slice list
     DevBuf ras_masks;                       // k_rasterize: key masks per workgroup (8 words), combined by k_reduce_masks
     PendingMasks pending_masks{nullptr, 0u}; // ... or, on read-back-free frames, by k_runs_count
@@ -182,7 +247,6 @@ struct forma_hip_ctx {
     bool have_unsorted = false;
     uint64_t live44 = 0xFFFFFFFFFFFull;     // varying bits of (v >> 20)
     bool layer_sorted = false;              // rasterizer stream is non-decreasing in layer
-    int digit_bits = 0;                     // radix digit width: 0 = 8, or 9 where that saves a pass (default); 4 / 8 / 9 forced (FORMA_HIP_DEBUG=digit_bits=)
     // paint
     DevBuf info_init;                       // pristine FrameInfo (reset template)
     // buffer-layer caches (reference cpu/buffer/mod.rs:113-197): per cache the CachedTile table, the device image the
@@ -199,10 +263,8 @@ struct forma_hip_ctx {
     TileCache caches[32];
     DevBuf pack_list, pack_pix;             // cache frames: written tiles of the crop (list + count word in front), their pixels packed
     DevBuf cache_written;                   // one byte per tile: written this frame
-    uint8_t* h_written = nullptr;           // pinned copy of cache_written
-    size_t h_written_cap = 0;
-    uint8_t* h_stage = nullptr;             // pinned staging image for tile-granular copy-out
-    size_t h_stage_cap = 0;
+    PinnedBuf h_written;                    // copy of cache_written
+    PinnedBuf h_stage;                      // staging image for tile-granular copy-out (released by trim: a whole 4K image after a cache frame)
     bool frame_has_dst = false;             // the frame being enqueued on this slot also copies its image out (forma_hip_render_enqueue)
     bool image_sent = false;                // a deferred frame into caller memory: its image left behind the kernels, before the frame was verified
     // A synchronous frame into caller memory (one frame in flight, no cache): the painter runs as two launches (tests: up to SPLIT_MAX) over
@@ -220,20 +282,11 @@ struct forma_hip_ctx {
     uint8_t* cur_image = nullptr;           // device image of the frame in flight / last frame
     bool image_external = false;            // ... is the caller's device target (forma_hip_render_device): forma_hip_read_image refuses it
     hipEvent_t wait_ev = nullptr;           // forma_hip_render_device's wait_stream: recorded there, waited for on the frame's stream
-    // sort-plan speculation: the varying-bit mask and the layer-sortedness of a scene rarely change between frames, so
-    // forma_hip_render plans the sort from the previous frame's values and verifies them when the frame is done
-    bool pred_valid = false, pred_layer_sorted = false, speculated = false;
-    bool global_runsort = false;           // FORMA_HIP_DEBUG=global_runsort: never order a row's runs in LDS (test switch)
-    bool pred_counts_valid = false, no_async = false;    // N / J predictions for read-back-free frames (FORMA_HIP_DEBUG=sync disables)
-    uint32_t pred_N = 0, pred_J = 0, pred_w = 0, pred_h = 0;
-    uint64_t pred_live44 = 0;
-    KeyRange pred_range{0, 0, 0, 0, false};  // what the tile fields spanned on the last verified frame (value-range digits, SortPlan::bias)
-    bool plan_biased = false; uint32_t bias_banned = 0, bias_ban_len = 0;   // bias_banned: frames left of a ban (re-armed with back-off: an animated scene
-                                                      // that left its span once gets the cheaper plan back), bias_ban_len: length of the last ban //   // this frame's plan leans on pred_range / a frame that did was void: plain digits for this geometry
+    Learned learned;                        // what verified frames taught this slot
+    bool speculated = false;                // this frame's sort was planned from learned.pred_live44 / pred_layer_sorted
+    bool plan_biased = false;               // this frame's plan leans on learned.pred_range
     bool seg_u_fused = false; uint32_t fused_w = 0, fused_h = 0;   // seg_u holds a fused frame's partitioned blocks (restore_unsorted)
     bool ras_fused = false;                 // ... and wrote its blocks partitioned by ras_plan's first digit (SliceSrc)
-    uint32_t pred_slice_len = 0;            // mean keys per (digit, block) slice of the last fused frame (0: not measured)
-    uint32_t fuse_skipped = 0;              // frames not fused since the slices were measured too short (FUSE_PROBE)
     bool ras_hist_on = false; SortPlan ras_plan;     // the rasterizer of this frame counted the digits of ras_plan into the sort's histograms (RasHist)
     const uint32_t* sort_range = nullptr;   // the tile-field spans the frame's sort leaves behind (k_runs_count folds them into FrameInfo) ...
     uint32_t sort_range_n = 0;              // ... one record per k_sort_hist workgroup
@@ -247,20 +300,17 @@ struct forma_hip_ctx {
     // which clear the words themselves when the pointer or the size is not what they need
     struct PreZero { const void* sort_p = nullptr; size_t sort_words = 0; const void* tab_p = nullptr; size_t tab_words = 0;
                      const void* chain_p = nullptr; size_t chain_words = 0; const void* slice_p = nullptr; size_t slice_words = 0; } pz;
-    ForMaDebug dbg;                         // FORMA_HIP_DEBUG as it stood when the context was created
+    ForMaDebug dbg;                         // FORMA_HIP_DEBUG as it stood when the context was created (a frame slot: its owner's) — the switches' one home
+    // radix digit width: 0 = 8, or 9 where that saves a pass (default); 4 / 8 / 9 forced (digit_bits=)
+    int digit_bits() const { return dbg.digit_bits == 4 || dbg.digit_bits == 8 || dbg.digit_bits == 9 ? dbg.digit_bits : 0; }
+    // carry_slices=N: that many workgroups per tile row in the carry pre-pass (0: by policy)
+    uint32_t force_slices() const { return dbg.carry_slices > 0 ? (uint32_t)std::min(dbg.carry_slices, (int)CR_MAX_SLICES_HOST) : 0u; }
     const uint32_t* chain_rows = nullptr;   // this frame's runs were numbered per tile row (launch_runs' chain): its row counts, for the
     uint32_t n_chain_rows = 0;              //   frame tail, which sums them into the host's n_runs
     uint32_t* h_rows = nullptr;             // pinned: runs per tile row (synchronous frames), 2049 words
-    uint32_t pred_max_row = 0xFFFFFFFFu;    // most runs in one tile row of the last verified frame (unknown: no local sort)
     // tiles deeper than the painter's LDS lists (finish_paint): what of the painter launch the context does not hold; the scratch lists
     struct HugeArgs { PaintParams P; DevCount jc; TileCacheArgs tc; uint32_t fmt; } huge{};
     DevBuf huge_offs, huge_key, huge_tmp, huge_flag;
-    // band
-    uint32_t band_row0 = 0, band_row1 = 0;
-    // a sub-range [line_lo, line_hi) of the uploaded lines (line i joins points i and i + 1) when line_ranged.
-    // A multi-device context uploads the whole geometry to every device and gives each its share of the LINES (multi.cpp).
-    bool line_ranged = false;
-    size_t line_lo = 0, line_hi = 0;
     // frames in flight inside ONE context (forma_hip_set_frames_in_flight): slots[0] is the context itself, the others are
     // full contexts (own stream, own per-frame buffers) that BORROW the scene buffers.  A device-resident, cache-less frame
     // is enqueued on the next slot and verified when that slot is needed again (or at any call that needs the result).
@@ -281,9 +331,6 @@ struct forma_hip_ctx {
     bool xpending = false;                    // a deferred owner's half (fd_gsp_defer) nobody has settled yet
     bool xoverflowed = false;                 // the last owner's half failed because a bucket outgrew the plan (FORMA_E_CAPACITY: re-plan)
     bool xuse_recv = false;                   // one rank, but a collective DID run (RCCL rehearsal): the buckets are in xrecv
-    bool xgather_always = false;              // FORMA_HIP_DEBUG=xgather: materialise the received stream before sorting it
-    bool xpred_valid = false;               // the local rasterized count of the previous exchange frame is known
-    uint32_t xpred_N = 0, xpred_w = 0, xpred_h = 0;
     uint32_t* h_xlocal = nullptr;           // pinned: [0] = local segment count of the last bucket frame (copied on the stream), [1] = 1 when pending
     // timing
     hipEvent_t ev0[ST_COUNT], ev1[ST_COUNT];
@@ -307,9 +354,12 @@ struct forma_hip_ctx {
         &x_spare, &y_spare, &line_slot_spare, &geo_blob, &geo_flag}; }
     // kept by trim, like the scene: FrameInfo and its template, cache frames' written-tile flags, the exchange's buckets
     std::vector<DevBuf*> kept_bufs() { return {&info, &info_init, &cache_written, &xsend, &xrecv}; }
+    std::vector<PinnedBuf*> pinned_bufs() { return {&h_written, &h_stage, &h_geo, &h_tab_stage}; }   // the growing page-locked ones
 };
 
 
+// the owner of the frame slots and every slot of it, the owner first (one frame in flight: the owner alone)
+inline std::vector<forma_hip_ctx*> frame_slots(forma_hip_ctx* o) { return o->slots.empty() ? std::vector<forma_hip_ctx*>{o} : o->slots; }
 inline uint32_t paint_strip_tiles(const forma_hip_ctx* c) { return c->n_cus * PAINT_WAVES_PER_CU; }
 
 #define FORMA_RETRY 1     /* internal: a speculation of the read-back-free path was wrong, run the frame again synchronously */

@@ -1,8 +1,8 @@
 // debug.h — the ONE place libforma_hip.so looks at the environment.
 //
 // FORMA_HIP_DEBUG = "name[=value],name,..." holds the switches tests and tools use to force or forbid one path each; a
-// deployment never sets it.  Parsed when a context is created (tests flip switches between contexts of one process), except
-// the two process-wide ones noted below.
+// deployment never sets it.  Parsed when a context is created (tests flip switches between contexts of one process; a frame
+// slot takes its owner's), except the two process-wide ones noted below.
 //   sync                 no read-back-free frames (every frame reads N, the key masks and J back)
 //   global_runsort       the carry pre-pass never orders a row's runs in LDS
 //   xgather              multi-GPU: always materialise the received stream before sorting it

@@ -753,7 +753,7 @@ int multi_set_geometry(forma_hip_ctx* ctx, const float* x, const float* y, const
 int multi_geometry_append(forma_hip_ctx* ctx, const forma_flatten_tables_t* t, const uint32_t* line_slot,
                           const forma_affine_range_t* affines, size_t n_affines) {
     MULTI_ENTER();
-    if (ctx->multi->kid[0]->n_points + t->n_points >= (1ull << 30)) return MFAIL(FORMA_E_ARG, "too many points");
+    if (ctx->multi->kid[0]->scene.n_points + t->n_points >= (1ull << 30)) return MFAIL(FORMA_E_ARG, "too many points");
     ctx->multi->planned = false;
     EACH_KID(forma_hip_geometry_append(k, t, line_slot, affines, n_affines));
     EACH_KID(fd_set_line_range(k, false, 0, 0));
@@ -770,7 +770,7 @@ int multi_geometry_retain(forma_hip_ctx* ctx, const forma_keep_range_t* keep, si
 int multi_counters(forma_hip_ctx* ctx, forma_counters_t* out) {
     MultiState* M = ctx->multi;
     *out = M->kid[0]->cnt;
-    out->geometry_points = M->kid[0]->n_points;
+    out->geometry_points = M->kid[0]->scene.n_points;
     out->frames = ctx->cnt.frames;                         // (the calls the context saw; a re-planned frame runs twice on the devices)
     out->geometry_bytes_h2d = 0; out->geometry_bytes_d2h = 0;
     for (int g = 0; g < M->G; g++) { out->geometry_bytes_h2d += M->kid[g]->cnt.geometry_bytes_h2d; out->geometry_bytes_d2h += M->kid[g]->cnt.geometry_bytes_d2h; }

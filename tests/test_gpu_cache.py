@@ -321,3 +321,51 @@ def test_damage_sets_of_random_scenes(seed):
             assert np.array_equal(wg.reshape(-1), c.tiles_written(w, h) != 0), (seed, frame_no)
     finally:
         c.close()
+
+
+def test_copy_out_buffers_grow_and_shrink_on_one_context():
+    """One context, cache frames into host memory at 64 x 64, then 256 x 192, then 64 x 64 again: the page-locked buffers behind the
+    copy-out (written-tile flags, staging image) are kept at the largest size seen and must serve the smaller canvas after the larger
+    one.  Per size: a fully repainted frame (one strided copy), a frame with one small changed layer (the packed tiles), one
+    with two larger changed layers, and a device-resident frame whose flags `tiles_written` fetches afterwards."""
+    import forma_amd
+    c = forma_amd.Context(0)
+    o = orc.Oracle()
+    clear = (0.9, 0.8, 0.7, 1.0)
+    dot = 10                                               # a small circle inside tile (1, 1), wherever it moves below
+    try:
+        for n_size, (w, h) in enumerate(((64, 64), (256, 192), (64, 64))):
+            comp = build(n=10, seed=40 + n_size, w=w, h=h)
+            comp.get_mut_or_insert_default(dot).insert(S.custom_circle(23.0, 23.0, 4.0)).set_props(S.solid((0.9, 0.1, 0.2, 1.0)))
+            tiles = ((w + 15) // 16) * ((h + 15) // 16)
+            for step, moved in enumerate((None, {dot}, {2, 5}, {dot})):
+                device_only = step == 3
+                set_unchanged(comp, moved is not None, except_orders=moved or ())
+                for k, m in enumerate(sorted(moved or ())):
+                    comp.layers[m].set_transform([1.0, 0.0, 0.0, 1.0, float(step), 1.0] if m == dot else [1.0, 0.0, 0.0, 1.0, 9.0 + 4 * k, -7.0])
+                t = comp.tables(o); S.load(o, t)
+                if moved is None:
+                    S.load(c, t)
+                else:
+                    c.set_geoms(t["geoms"]); c.set_styles(t["style_offsets"], t["style_words"], t["unchanged"])
+                sent = [np.full((h, w * 4), 201, np.uint8), np.full((h, w * 4), 201, np.uint8)]
+                o.render(w, h, clear=clear, cache_id=4, dst=sent[0])
+                if device_only:
+                    c.render(w, h, clear=clear, cache_id=4, device_only=True)
+                else:
+                    c.render(w, h, clear=clear, cache_id=4, dst=sent[1])
+                wo = _written(sent[0], 201, w, h)
+                assert np.array_equal(wo.reshape(-1), c.tiles_written(w, h) != 0), (w, h, step)
+                if step == 0:
+                    assert wo.all(), (w, h)                                # everything painted: the strided copy
+                elif moved == {dot}:
+                    assert 0 < wo.sum() <= max(tiles // 4, 1), (w, h, step, int(wo.sum()))    # few tiles: the packed copy
+                got = c.read_image(w, h) if device_only else sent[1]
+                if device_only:                                            # (the cache's image: compared where this frame wrote)
+                    m = np.repeat(np.repeat(wo, 16, axis=0), 16 * 4, axis=1)[:h, :w * 4]
+                    assert np.abs(got[m].astype(int) - sent[0][m].astype(int)).max() <= 1, (w, h, step)
+                else:
+                    assert np.array_equal(wo, _written(got, 201, w, h)), (w, h, step)
+                    assert np.abs(got.astype(int) - sent[0].astype(int)).max() <= 1, (w, h, step)
+    finally:
+        c.close()

@@ -62,9 +62,8 @@ int frame_tail(forma_hip_ctx* ctx, bool to_host_info, uint32_t* host_count) {
     const bool timed = ctx->stage_used[ST_PAINT];         // (a timed frame books the tail on the paint stage)
     stage_begin(ctx, ST_PAINT, timed);
     launch_frame_tail(ctx->stream, ctx->info.as<FrameInfo>(), to_host_info ? ctx->h_info : nullptr, host_count,
-                      ctx->order_cnt_dev, ctx->order_keep_dev, ctx->chain_rows, ctx->n_chain_rows,
+                      take(ctx->hand.order_cnt_dev), take(ctx->hand.order_keep_dev), take(ctx->hand.chain_rows), take(ctx->hand.n_chain_rows),
                       to_host_info ? ctx->h_seq : nullptr, to_host_info ? ++ctx->tail_seq : 0u);
-    ctx->order_cnt_dev = nullptr; ctx->order_keep_dev = nullptr; ctx->chain_rows = nullptr; ctx->n_chain_rows = 0;
     stage_end(ctx, ST_PAINT, timed);
     HIPCHECK(hipGetLastError());
     ctx->info_clean = true;
@@ -133,24 +132,27 @@ int finish_rasterize(forma_hip_ctx* ctx) {
 SortPlan frame_sort_plan(forma_hip_ctx* ctx, uint64_t live44, bool layer_sorted, int digit_bits, bool speculated, bool* biased);
 static bool fuse_plan_ok(const forma_hip_ctx* ctx, const SortPlan& plan);
 
+// A stream begins (the rasterizer's, a caller's or the exchange's segments): nothing has been handed over — cleared ahead of its
+// stage, counted or left behind by an earlier stage — and no sort plan has been guessed
+inline void begin_stream(forma_hip_ctx* ctx) { ctx->hand = HandOffs(); ctx->guess.speculated = false; }
+
 // stages 1-2 on the uploaded geometry: line table + rasterize -> seg_u.
 // bound_n != 0: fully asynchronous (no read-back): N is only known to the device, buffers / grids are provisioned for
 // bound_n segments, the sort plan is the speculated one.
 int run_rasterize_frame(forma_hip_ctx* ctx, uint32_t width, uint32_t height, bool timing, bool speculate = false,
-                        uint32_t bound_n = 0, const ZeroJobs* zero = nullptr, const forma_hip_ctx::PreZero* cleared = nullptr,
+                        uint32_t bound_n = 0, const ZeroJobs* zero = nullptr, const PreZero* cleared = nullptr,
                         bool hist_too = false /* count the speculated sort plan's digits while the keys are made (RasHist) */) {
     const size_t all_lines = ctx->scene.n_points ? ctx->scene.n_points - 1 : 0;
     const size_t n_lines = ctx->scene.line_ranged ? std::min(ctx->scene.line_hi, all_lines) - std::min(ctx->scene.line_lo, all_lines) : all_lines;
     ctx->n_lines = n_lines;
     ctx->n_seg = 0; ctx->n_compact = 0; ctx->have_unsorted = true; ctx->live44 = 0; ctx->layer_sorted = true;
-    ctx->speculated = false; ctx->ras_hist_on = false; ctx->ras_fused = false;
-    ctx->pz = forma_hip_ctx::PreZero();                   // (nothing of this frame has been cleared ahead of its stage yet)
+    begin_stream(ctx);
     int rc = reset_info(ctx);
     if (rc) return rc;
-    if (n_lines == 0) return FORMA_OK;
+    if (n_lines == 0) return FORMA_OK;                    // (no stream: "nothing handed over" is what the later stages see)
     const LineSource S = geometry_source(ctx, width, height);
     if ((rc = run_line_table(ctx, S, n_lines, timing, bound_n, zero))) return rc;
-    if (zero && cleared) ctx->pz = *cleared;              // (k_line_len ran: the words of `zero` are cleared for the later stages)
+    if (zero && cleared) ctx->hand.pz = *cleared;         // (k_line_len ran: the words of `zero` are cleared for the later stages)
     FrameInfo* dinfo = ctx->info.as<FrameInfo>();
     DevCount nc_seg, nc_cmp;
     if (bound_n) {
@@ -169,16 +171,16 @@ int run_rasterize_frame(forma_hip_ctx* ctx, uint32_t width, uint32_t height, boo
     // the plan the sort will use if the speculation holds (run_sort checks that it is the same plan)
     RasHist RH;
     memset(&RH, 0, sizeof RH);
-    if (hist_too && bound_n && ctx->learned.pred_valid && ctx->pz.sort_p && ctx->pz.sort_p == ctx->sort_counters.p && !ctx->dbg.no_ras_hist) {
-        ctx->ras_plan = frame_sort_plan(ctx, ctx->learned.pred_live44, ctx->learned.pred_layer_sorted, ctx->digit_bits(), true, nullptr);
-        RH = make_ras_hist(ctx->ras_plan, ctx->sort_counters.as<uint32_t>());
-        ctx->ras_hist_on = RH.hist != nullptr;
+    HandOffs& hand = ctx->hand;
+    if (hist_too && bound_n && ctx->learned.pred_valid && hand.pz.sort.p && hand.pz.sort.p == ctx->sort_counters.p && !ctx->dbg.no_ras_hist) {
+        hand.ras_plan = frame_sort_plan(ctx, ctx->learned.pred_live44, ctx->learned.pred_layer_sorted, ctx->digit_bits(), true, nullptr);
+        RH = make_ras_hist(hand.ras_plan, ctx->sort_counters.as<uint32_t>());
+        hand.ras_hist_on = RH.hist != nullptr;
         // ... and the first digit pass with them, where the frame's first kernel cleared the slice table for this bound
-        if (RH.hist && ctx->pz.slice_p && ctx->pz.slice_p == ctx->slice_buf.p && ctx->pz.slice_words >= slice_tab_words(bound_n) &&
-            fuse_plan_ok(ctx, ctx->ras_plan)) {
+        if (RH.hist && hand.pz.slice.p && hand.pz.slice.covers(ctx->slice_buf.p, slice_tab_words(bound_n)) && fuse_plan_ok(ctx, hand.ras_plan)) {
             const SliceSrc SS = make_slice_src(ctx->slice_buf.as<uint32_t>(), bound_n);
             RH.slice_tab = SS.tab; RH.tab_stride = SS.tab_stride; RH.rank_mode = (uint32_t)ctx->dbg.ras_rank;
-            ctx->ras_fused = true;
+            hand.ras_fused = true;
         }
         // the tile fields' spans are worth measuring only where a biased plan could ever beat the plain one: the plain digits of
         // the tile fields take more than two passes (canvases beyond 255 tiles in a dimension), or this frame's plan is biased
@@ -187,7 +189,7 @@ int run_rasterize_frame(forma_hip_ctx* ctx, uint32_t width, uint32_t height, boo
             const SortPlan plain = make_segment_sort_plan(ctx->learned.pred_live44, ctx->learned.pred_layer_sorted, ctx->digit_bits(), nullptr, nullptr);
             const SortPlan lay = ctx->learned.pred_layer_sorted ? SortPlan{} : make_sort_plan((ctx->learned.pred_live44 & 0x1FFFFFull) << 20, 20, 41, ctx->digit_bits());
             bool biased = false;
-            for (int p = 0; p < ctx->ras_plan.n_passes; p++) biased |= ctx->ras_plan.fmask[p] != 0u;
+            for (int p = 0; p < hand.ras_plan.n_passes; p++) biased |= hand.ras_plan.fmask[p] != 0u;
             RH.track_range = (biased || plain.n_passes > (ctx->learned.pred_layer_sorted ? 0 : lay.n_passes) + 2) ? 1u : 0u;
         }
     }
@@ -196,12 +198,12 @@ int run_rasterize_frame(forma_hip_ctx* ctx, uint32_t width, uint32_t height, boo
                      ctx->block_first.as<uint32_t>(), ctx->seg_u.as<uint64_t>(), dinfo, (int)ctx->scene.band_row0,
                      (int)ctx->scene.band_row1, ctx->ras_masks.as<uint32_t>(), /*reduce_now=*/bound_n == 0, &RH);
     // read-back-free frame: the masks stay per-workgroup records until k_runs_count combines them (nothing reads them earlier)
-    ctx->pending_masks = bound_n ? PendingMasks{ctx->ras_masks.as<uint32_t>(), 0u, ctx->ras_hist_on ? 1u : 0u} : PendingMasks{nullptr, 0u, 0u};
-    ctx->seg_u_fused = ctx->ras_fused; ctx->fused_w = width; ctx->fused_h = height;
+    if (bound_n) hand.pending_masks = PendingMasks{ctx->ras_masks.as<uint32_t>(), 0u, hand.ras_hist_on ? 1u : 0u};
+    ctx->seg_u_fused = hand.ras_fused; ctx->fused_w = width; ctx->fused_h = height;
     stage_end(ctx, ST_RASTER, timing);
     HIPCHECK(hipGetLastError());
-    ctx->speculated = (speculate || bound_n) && ctx->learned.pred_valid;
-    if (ctx->speculated) {
+    ctx->guess.speculated = (speculate || bound_n) && ctx->learned.pred_valid;
+    if (ctx->guess.speculated) {
         ctx->live44 = ctx->learned.pred_live44; ctx->layer_sorted = ctx->learned.pred_layer_sorted;
         // (asynchronous frames: k_runs_count verifies the plan on the device before anything relies on the sort order)
         return FORMA_OK;
@@ -227,11 +229,11 @@ int run_rasterize_frame(forma_hip_ctx* ctx, uint32_t width, uint32_t height, boo
 // frame's kernels, not by the passes alone.  A frame whose image also crosses PCIe behind its kernels (forma_hip_render_enqueue)
 // keeps all CUs: there the passes are on the frame's critical path (two slots: 1 453 -> 1 134 frames/s with half of them).
 // FORMA_HIP_DEBUG=sort_cus=N sets it (0: all).
-static uint32_t sort_workgroups(const forma_hip_ctx* ctx, size_t n_keys) {
+static uint32_t sort_workgroups(const forma_hip_ctx* ctx, size_t n_keys, FrameMode mode) {
     if (ctx->dbg.sort_cus >= 0) return (uint32_t)ctx->dbg.sort_cus;
     const forma_hip_ctx* o = ctx->owner ? ctx->owner : ctx;
     const size_t slots = o->slots.size();
-    if (ctx->frame_has_dst) return 0u;
+    if (mode.has_dst) return 0u;
     return slots == 3 || (slots == 2 && n_keys >= ((size_t)1 << 22)) ? o->n_cus / 2u : 0u;
 }
 
@@ -316,9 +318,9 @@ static bool fuse_first_digit(forma_hip_ctx* ctx, const SortPlan& plan) {
 // dispatch of its own.  The buffers are grown here, before anything of the frame is enqueued, so that the stages' own
 // `ensure` calls find them in place.  `sort_n`: the keys the frame's sort will see (its provisioning bound).
 int plan_zero_jobs(forma_hip_ctx* ctx, uint32_t width, uint32_t height, uint32_t sort_n, uint32_t runs_n, ZeroJobs* Z,
-                   forma_hip_ctx::PreZero* cleared) {
+                   PreZero* cleared) {
     memset(Z, 0, sizeof *Z);
-    *cleared = forma_hip_ctx::PreZero();
+    *cleared = {};
     if (ctx->dbg.no_prezero) return FORMA_OK;
     const uint32_t tiles_w = (width + 15) / 16, tiles_h = (height + 15) / 16;
     const SortPlan plan = frame_sort_plan(ctx, ctx->learned.pred_live44, ctx->learned.pred_layer_sorted, ctx->digit_bits(), true, nullptr);
@@ -329,23 +331,23 @@ int plan_zero_jobs(forma_hip_ctx* ctx, uint32_t width, uint32_t height, uint32_t
     const size_t sw = sort_n > 1 && plan.n_passes ? sort_zero_words(sort_n, plan) : 0;
     const size_t tw = tab.zero_words;
     if (sw > 0xFFFFFFFFull || tw > 0xFFFFFFFFull) return FORMA_OK;           // (absurd sizes: the stages clear for themselves)
-    if (sw) { Z->p[Z->n] = ctx->sort_counters.as<uint32_t>(); Z->words[Z->n++] = (uint32_t)sw; cleared->sort_p = ctx->sort_counters.p; cleared->sort_words = sw; }
-    Z->p[Z->n] = tab.row_count; Z->words[Z->n++] = (uint32_t)tw; cleared->tab_p = ctx->row_tab.p; cleared->tab_words = tw;
+    if (sw) { Z->p[Z->n] = ctx->sort_counters.as<uint32_t>(); Z->words[Z->n++] = (uint32_t)sw; cleared->sort = Cleared{ctx->sort_counters.p, sw}; }
+    Z->p[Z->n] = tab.row_count; Z->words[Z->n++] = (uint32_t)tw; cleared->tab = Cleared{ctx->row_tab.p, tw};
     // (the status words of the chained run kernel: a word per 2 048 segments)
     const size_t cw = runs_n ? runs_chain_words(runs_n) : 0;
-    if (cw && cw <= 0xFFFFFFFFull) { Z->p[Z->n] = ctx->runs_scratch.as<uint32_t>(); Z->words[Z->n++] = (uint32_t)cw; cleared->chain_p = ctx->runs_scratch.p; cleared->chain_words = cw; }
+    if (cw && cw <= 0xFFFFFFFFull) { Z->p[Z->n] = ctx->runs_scratch.as<uint32_t>(); Z->words[Z->n++] = (uint32_t)cw; cleared->chain = Cleared{ctx->runs_scratch.p, cw}; }
     // (the slice table of a fused first digit pass)
     if (sw && Z->n < FORMA_ZERO_JOBS && fuse_first_digit(ctx, plan) && slice_tab_words(sort_n) <= 0xFFFFFFFFull) {
         HIPCHECK(ctx->slice_buf.ensure(slice_scratch_words(sort_n) * 4));
         const size_t lw = slice_tab_words(sort_n);
-        Z->p[Z->n] = ctx->slice_buf.as<uint32_t>(); Z->words[Z->n++] = (uint32_t)lw; cleared->slice_p = ctx->slice_buf.p; cleared->slice_words = lw;
+        Z->p[Z->n] = ctx->slice_buf.as<uint32_t>(); Z->words[Z->n++] = (uint32_t)lw; cleared->slice = Cleared{ctx->slice_buf.p, lw};
     }
     return FORMA_OK;
 }
 
 // stage 3 on `src` (nc segments, device): result pointer in ctx->sorted
 int run_sort(forma_hip_ctx* ctx, const uint64_t* src, DevCount nc, bool timing, int digit_bits = 0,
-             const ChunkedSrc* chunked = nullptr) {
+             const ChunkedSrc* chunked = nullptr, FrameMode mode = {}) {
     ctx->n_passes = 0;
     const size_t n = nc.bound;
     if (n >= (1ull << 30)) return fail(ctx, FORMA_E_CAPACITY, "more than 2^30-1 pixel segments on one device");
@@ -353,38 +355,36 @@ int run_sort(forma_hip_ctx* ctx, const uint64_t* src, DevCount nc, bool timing, 
     HIPCHECK(ctx->seg_a.ensure((std::max<size_t>(n, 1) + SEG_PAD) * 8));
     HIPCHECK(ctx->seg_b.ensure((std::max<size_t>(n, 1) + SEG_PAD) * 8));
     HIPCHECK(ctx->sort_counters.ensure(sort_scratch_words(std::max<size_t>(n, 1)) * 4));
-    const SortPlan plan = frame_sort_plan(ctx, ctx->live44, ctx->layer_sorted, digit_bits, ctx->speculated && nc.ptr != nullptr, &ctx->plan_biased);
+    HandOffs& hand = ctx->hand;
+    const SortPlan plan = frame_sort_plan(ctx, ctx->live44, ctx->layer_sorted, digit_bits, ctx->guess.speculated && nc.ptr != nullptr, &ctx->guess.plan_biased);
     ctx->n_passes = plan.n_passes;
-    ctx->sort_range = n > 1 && plan.n_passes ? sort_range_words(ctx->sort_counters.as<uint32_t>()) : nullptr;
-    ctx->sort_range_n = sort_hist_blocks(n);
-    bool zeroed = ctx->pz.sort_p == ctx->sort_counters.p && ctx->pz.sort_words >= sort_zero_words(n, plan);
-    ctx->pz.sort_p = nullptr;
+    hand.sort_range = n > 1 && plan.n_passes ? sort_range_words(ctx->sort_counters.as<uint32_t>()) : nullptr;
+    hand.sort_range_n = sort_hist_blocks(n);
+    bool zeroed = take(hand.pz.sort).covers(ctx->sort_counters.p, sort_zero_words(n, plan));
     // did the rasterizer count exactly this plan's digits?  (if it counted another plan's, the scratch is no longer clear)
-    bool hist_ready = ctx->ras_hist_on && zeroed && !chunked && plan.n_passes == ctx->ras_plan.n_passes && src == ctx->seg_u.as<uint64_t>();
+    const bool ras_hist = take(hand.ras_hist_on), ras_fused = take(hand.ras_fused);
+    const SortPlan& rp = hand.ras_plan;
+    bool hist_ready = ras_hist && zeroed && !chunked && plan.n_passes == rp.n_passes && src == ctx->seg_u.as<uint64_t>();
     for (int p = 0; hist_ready && p < plan.n_passes; p++)
-        hist_ready = plan.shift[p] == ctx->ras_plan.shift[p] && plan.mask[p] == ctx->ras_plan.mask[p] && plan.bias[p] == ctx->ras_plan.bias[p] &&
-                     plan.fmask[p] == ctx->ras_plan.fmask[p];
-    if (ctx->ras_hist_on && !hist_ready) zeroed = false;
-    ctx->ras_hist_on = false;
+        hist_ready = plan.shift[p] == rp.shift[p] && plan.mask[p] == rp.mask[p] && plan.bias[p] == rp.bias[p] && plan.fmask[p] == rp.fmask[p];
+    if (ras_hist && !hist_ready) zeroed = false;
     // the rasterizer partitioned its blocks by the first digit: only the sort it planned for may read them (never met: the plan is
     // the same function of the same predictions; should it differ, the frame is void and runs again synchronously)
-    const bool fused = ctx->ras_fused && hist_ready;
-    if (ctx->ras_fused && !fused) HIPCHECK(hipMemsetAsync(&ctx->info.as<FrameInfo>()->plan_bad, 1, 4, ctx->stream));
-    ctx->ras_fused = false;
+    const bool fused = ras_fused && hist_ready;
+    if (ras_fused && !fused) HIPCHECK(hipMemsetAsync(&ctx->info.as<FrameInfo>()->plan_bad, 1, 4, ctx->stream));
     SliceSrc SS;
     if (fused) SS = make_slice_src(ctx->slice_buf.as<uint32_t>(), n);
-    if (hist_ready) ctx->sort_range = nullptr;               // (the spans travel in the rasterizer's mask records: PendingMasks::has_range)
+    if (hist_ready) hand.sort_range = nullptr;               // (the spans travel in the rasterizer's mask records: PendingMasks::has_range)
     stage_begin(ctx, ST_SORT, timing);
     ctx->sorted = (uint64_t*)launch_radix_sort(ctx->stream, src, ctx->seg_a.as<uint64_t>(), ctx->seg_b.as<uint64_t>(), nc, plan,
                                                digit_bits, ctx->sort_counters.as<uint32_t>(), &ctx->info.as<FrameInfo>()->error,
                                                chunked,
-                                               ctx->info.as<FrameInfo>(), zeroed, hist_ready, sort_workgroups(ctx, n),
+                                               ctx->info.as<FrameInfo>(), zeroed, hist_ready, sort_workgroups(ctx, n, mode),
                                                fused ? &SS : nullptr);
     stage_end(ctx, ST_SORT, timing);
     HIPCHECK(hipGetLastError());
     return FORMA_OK;
 }
-
 
 // h_info holds a fresh copy of the device FrameInfo: remember the sort-plan inputs of this frame and, if the plan was
 // speculated from the previous frame, verify it.  Called at the run-count read-back, i.e. BEFORE any kernel that
@@ -396,7 +396,7 @@ int verify_speculation(forma_hip_ctx* ctx) {
     if (k_or == 0 && k_and == ~0ull) return FORMA_OK;            // masks untouched: the rasterizer did not run this frame
     const uint64_t live = (k_or ^ k_and) & 0xFFFFFFFFFFFull;
     const bool sorted = ctx->h_info->layer_unsorted == 0;
-    const bool wrong = ctx->speculated && (live != ctx->live44 || sorted != ctx->layer_sorted);
+    const bool wrong = ctx->guess.speculated && (live != ctx->live44 || sorted != ctx->layer_sorted);
     ctx->learned.pred_valid = true; ctx->learned.pred_live44 = live; ctx->learned.pred_layer_sorted = sorted;
     return wrong ? FORMA_RETRY : FORMA_OK;
 }
@@ -412,11 +412,11 @@ TileRect crop_tiles(const PaintArgs& a) {
 // of kernels.  Painted in bands of tile rows — one launch and one event per band — the first band's pixels leave after an
 // eighth of the painter instead, on a second stream, and the link is busy while the rest is painted (the copies then end ~70 us
 // earlier; what the bands cost the painter — no heavy-first order across launches, eight tails — hides under the copy).
-// Only read-back-free frames that enqueue_own verifies at once and that deliver into `dst` ask for it (split_want), never with a cache (the written-tile
+// Only read-back-free frames that enqueue_own verifies at once and that deliver into `dst` ask for it (FrameMode::may_split), never with a cache (the written-tile
 // set decides what is copied) and not for images of a few MB.  Returns the number of bands, 0: one launch as ever.
 #define SPLIT_MIN_RUNS 262144u
-int split_plan(forma_hip_ctx* ctx, const PaintArgs& a, const PaintParams& P, uint32_t bound_j, bool timing) {
-    if (!ctx->split_want || !bound_j || timing || a.cache_id >= 0 || ctx->dbg.paint_split == 0) return 0;
+int split_plan(forma_hip_ctx* ctx, const PaintArgs& a, const PaintParams& P, uint32_t bound_j, bool timing, bool may_split) {
+    if (!may_split || !bound_j || timing || a.cache_id >= 0 || ctx->dbg.paint_split == 0) return 0;
     const uint32_t rows = P.crop_y1 > P.crop_y0 ? P.crop_y1 - P.crop_y0 : 0u;
     const uint32_t cols = P.crop_x1 > P.crop_x0 ? P.crop_x1 - P.crop_x0 : 0u;
     const bool forced = ctx->dbg.paint_split > 1;
@@ -427,7 +427,7 @@ int split_plan(forma_hip_ctx* ctx, const PaintArgs& a, const PaintParams& P, uin
     if (rows < 2u) return 0;
     if (!ctx->copy_stream) {
         if (hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking) != hipSuccess) { ctx->copy_stream = nullptr; return 0; }
-        for (int k = 0; k < forma_hip_ctx::SPLIT_MAX; k++)
+        for (int k = 0; k < SPLIT_MAX; k++)
             if (hipEventCreateWithFlags(&ctx->split_ev[k], hipEventDisableTiming) != hipSuccess) {
                 ctx->split_ev[k] = nullptr;
                 for (int q = 0; q < k; q++) { (void)hipEventDestroy(ctx->split_ev[q]); ctx->split_ev[q] = nullptr; }   // (no stream: one launch as ever)
@@ -468,13 +468,6 @@ int paint_target(forma_hip_ctx* ctx, const PaintArgs& a, PaintTarget* out) {
     }
     return FORMA_OK;
 }
-// How the frame's runs are numbered (launch_runs) and which carry kernel orders them (launch_carry_rows)
-struct CarryPlan {
-    bool local_sort;                        // the rows' runs are ordered inside k_carry_rows (else by a global radix sort)
-    bool chain, chain_zero, blk;            // numbered per tile row (its status words cleared by the frame's first kernel) / per 2 048-segment tile
-    uint32_t rows_painted, n_slices;        // tile rows the carry pre-pass visits, its workgroups per row
-    bool small, half, covl;                 // the carry kernel's variant
-};
 // Slicing pays when a row is heavy (measured on a 17-row band of the 4K scene, 4 800 runs per row: carry stage 80 -> 57 us
 // with eight small workgroups per row) and costs when it is light (a 64-row band of the 8192 x 8192 scene, ~1 000 runs per
 // row: 48 -> 55 us): a slice should keep >= ~768 runs.
@@ -510,15 +503,14 @@ CarryPlan plan_carry(forma_hip_ctx* ctx, const PaintArgs& a, size_t n, uint32_t 
     cp.chain = bound_j != 0 && n > 0 && cp.local_sort && ctx->learned.pred_max_row <= carry_rows_local_cap() &&
                (ctx->dbg.runs_chain < 0 ? (RUNS_CHAIN_DEFAULT != 0 && runs_chain_words(n) <= RUNS_CHAIN_MAX_TILES && one_frame_in_flight(ctx))
                                         : ctx->dbg.runs_chain != 0);
-    cp.chain_zero = cp.chain && ctx->pz.chain_p == ctx->runs_scratch.p && ctx->pz.chain_words >= runs_chain_words(n);
-    ctx->pz.chain_p = nullptr;
+    const bool chain_cleared = take(ctx->hand.pz.chain).covers(ctx->runs_scratch.p, runs_chain_words(n));
+    cp.chain_zero = cp.chain && chain_cleared;
     // Several workgroups share a tile row, each a range of layers (k_carry_rows): as many as keep the chip busy for the rows
     // this frame paints (a multi-GPU band is a fraction of the canvas).  The small-LDS variant (a quarter of the keys per workgroup) is a
     // read-back-free frame's guess — its slices must fit 4096 runs, known only from a previous frame; a slice that does not
     // fit voids the frame (plan_bad), the synchronous re-run takes the large variant, and the guess is not made again.
     const TileRect crop = crop_tiles(a);                  // (the tile rows the painter visits)
     cp.rows_painted = std::max(crop.y1 > crop.y0 ? crop.y1 - crop.y0 : 0u, 1u);
-    ctx->cur_rows_painted = cp.rows_painted;
     cp.n_slices = 1;
     if (bound_j) {
         cp.local_sort = cp.local_sort && ctx->learned.pred_max_row <= carry_rows_local_cap();     // wrong guess -> plan_bad -> synchronous re-run
@@ -549,7 +541,6 @@ CarryPlan plan_carry(forma_hip_ctx* ctx, const PaintArgs& a, size_t n, uint32_t 
             const uint64_t guess = known ? (uint64_t)ctx->learned.pred_max_slice * 10 / 9 : (kh > 1u ? (uint64_t)pmr * 5 / (3 * kh) : (uint64_t)pmr * 6 / 5);
             if (guess <= carry_rows_half_cap()) { cp.small = true; cp.half = true; cp.n_slices = kh; }
         }
-        ctx->small_tried = cp.small;
     }
     // BLOCKS (launch_runs, k_carry_rows): a read-back-free frame whose tile rows take ONE carry workgroup each needs neither the counting
     // pass nor the chain: the run kernel numbers per 2 048-segment tile into sparse arrays and the row's workgroup compacts them.
@@ -575,9 +566,7 @@ void replan_carry(forma_hip_ctx* ctx, CarryPlan* cp, uint32_t max_row) {
 // the final slice count and the COVL choice with it, once the frame has runs
 void settle_carry(forma_hip_ctx* ctx, CarryPlan* cp, uint32_t bound_j) {
     if (ctx->force_slices()) cp->n_slices = ctx->force_slices();  // FORMA_HIP_DEBUG=carry_slices (tests: every slice count on one GPU)
-    ctx->cur_slices = cp->n_slices; ctx->cur_small = cp->small; ctx->cur_half = cp->half;
     cp->covl = covl_choice(ctx, *cp, cp->n_slices, bound_j != 0);
-    ctx->covl_tried = cp->covl && bound_j != 0;
 }
 // The frame's runs (launch_runs) as `cp` numbers them; *jc: their count as the later stages see it, *J: as the host knows it (0: not).
 // Records, run keys and digests are sized for the RUNS, not for the segments (a run needs a segment, so N would always do: 440 MB of
@@ -592,18 +581,20 @@ int number_runs(forma_hip_ctx* ctx, DevCount nc, const PaintArgs& a, const Frame
     *J = 0;
     if (bound_j) {
         *jc = chain ? DevCount{nullptr, (uint32_t)n} : (blk ? DevCount{nullptr, bound_j} : DevCount{&dinfo->n_runs, bound_j});   // (chain: run indices are segment indices; blk: dense, counted by nobody before the tail)
-        if (chain || blk) { ctx->chain_rows = tab.row_count; ctx->n_chain_rows = tiles_h; }
+        if (chain || blk) { ctx->hand.chain_rows = tab.row_count; ctx->hand.n_chain_rows = tiles_h; }
     }
     size_t cap = std::max<size_t>(chain ? n : bound_j, 1);
+    const PendingMasks masks = take(ctx->hand.pending_masks);
+    const uint32_t* const sort_range = take(ctx->hand.sort_range);
     auto runs = [&](int what) {
         launch_runs(ctx->stream, ctx->sorted, nc, tiles_w, tiles_h, blk ? ctx->rec_sp.as<TileRecord>() : ctx->records.as<TileRecord>(), (uint32_t)(blk ? n : cap),
                     ctx->rk_u.as<uint64_t>(), ctx->blk_edge.as<BlkEdge>(), tab,
-                    ctx->runs_scratch.as<uint32_t>(), dinfo, /*verify_plan=*/bound_j != 0 && ctx->speculated, ctx->live44,
-                    ctx->layer_sorted, ctx->pending_masks,
+                    ctx->runs_scratch.as<uint32_t>(), dinfo, /*verify_plan=*/bound_j != 0 && ctx->guess.speculated, ctx->live44,
+                    ctx->layer_sorted, masks,
                     RunStyle{ctx->layer_sf.as<uint32_t>(), (uint32_t)ctx->scene.n_orders,
                              (a.cache_id >= 0 && ctx->scene.have_unchanged) ? ctx->unchanged.as<uint8_t>() : nullptr,
                              blk ? ctx->run_lt_sp.as<uint32_t>() : ctx->run_lt.as<uint32_t>()},
-                    tables_zero, ctx->sort_range, ctx->sort_range_n, what, chain ? tab.row_base : (blk ? ctx->row_sp.as<uint32_t>() : nullptr), cp->chain_zero, blk);
+                    tables_zero, sort_range, ctx->hand.sort_range_n, what, chain ? tab.row_base : (blk ? ctx->row_sp.as<uint32_t>() : nullptr), cp->chain_zero, blk);
     };
     if (!bound_j && n > 0) {
         runs(1);
@@ -629,8 +620,6 @@ int number_runs(forma_hip_ctx* ctx, DevCount nc, const PaintArgs& a, const Frame
         HIPCHECK(ctx->row_sp.ensure(((size_t)tiles_h + 1) * 4));
     }
     runs(bound_j || n == 0 ? 3 : 2);
-    ctx->sort_range = nullptr;
-    ctx->pending_masks = PendingMasks{nullptr, 0u};
     HIPCHECK(hipGetLastError());
     if (bound_j) return FORMA_OK;
     if (n > 0) {
@@ -682,7 +671,6 @@ int provision_spans(forma_hip_ctx* ctx, DevCount jc, uint32_t tiles_w, uint32_t 
         *sorted_keys = launch_radix_sort(ctx->stream, ctx->rk_u.as<uint64_t>(), ctx->rk_a.as<uint64_t>(),
                                          ctx->rk_b.as<uint64_t>(), jc, rk_plan, ctx->digit_bits(),
                                          ctx->sort_counters.as<uint32_t>(), &ctx->info.as<FrameInfo>()->error, nullptr, nullptr);
-        ctx->pz.sort_p = nullptr;
     }
     return FORMA_OK;
 }
@@ -711,13 +699,12 @@ PaintParams paint_params(const forma_hip_ctx* ctx, const PaintArgs& a, uint32_t 
 }
 // heaviest tiles first (PaintParams::order_*): read-back-free frames without a cache, one wavefront per tile
 int heavy_order(forma_hip_ctx* ctx, const PaintArgs& a, uint32_t bound_j, DevCount jc, const FrameTables& tab, uint32_t tiles_painted,
-                bool strips, bool quads, int split_n, PaintParams* P) {
-    ctx->order_pending = -1; ctx->order_cnt_dev = nullptr; ctx->order_keep_dev = nullptr;
+                bool strips, bool quads, int split_n, bool tail, PaintParams* P) {
     if (ctx->dbg.order_thr >= 0) ctx->learned.order_off = 0;
     if (ctx->learned.order_off) ctx->learned.order_off--;                 // (a flat scene: the order is retried every 256 frames)
     // ... of launches that are a handful of rounds of wavefronts: one tile's life is then a good part of the launch's.  A frame
     // of 32 rounds (the 8K scene: 262 144 tiles on 8 192 wave slots) has no tail worth 10 % of bookkeeping.
-    if (!(ctx->order_enable && bound_j && a.cache_id < 0 && !strips && !quads && !ctx->dbg.no_order && jc.bound > 0 && tiles_painted && !ctx->learned.order_off && split_n == 0 &&
+    if (!(tail && bound_j && a.cache_id < 0 && !strips && !quads && !ctx->dbg.no_order && jc.bound > 0 && tiles_painted && !ctx->learned.order_off && split_n == 0 &&
           tiles_painted <= 16u * paint_strip_tiles(ctx) && (one_frame_in_flight(ctx) || ctx->dbg.order_thr >= 0))) { ctx->learned.order_cur = -1; return FORMA_OK; }   // (any other frame in between: the lists are stale)
     // (heavy section: an eighth of the band's tiles, as PAINT_ORDER_SUBS lists of equal capacity)
     const size_t per = paint_band_tiles(P->crop_y1 > P->crop_y0 ? P->crop_y1 - P->crop_y0 : 0u, P->tiles_w), hcap = std::max<size_t>((per / 8 + PAINT_ORDER_SUBS - 1) / PAINT_ORDER_SUBS, 2) * PAINT_ORDER_SUBS;
@@ -739,8 +726,8 @@ int heavy_order(forma_hip_ctx* ctx, const PaintArgs& a, uint32_t bound_j, DevCou
     P->order_cnt_out = tab.order_cnt; P->order_list_out = wset + PAINT_ORDER_WORDS;
     P->order_flag_out = reinterpret_cast<uint8_t*>(wset + PAINT_ORDER_WORDS + 8 * hcap);
     P->order_hcap = (uint32_t)hcap; P->order_thr = ctx->dbg.order_thr >= 0 ? (uint32_t)ctx->dbg.order_thr : ctx->learned.order_thr;
-    ctx->order_pending = w; ctx->order_pending_sig = sig; ctx->order_tiles = tiles_painted;
-    ctx->order_cnt_dev = tab.order_cnt; ctx->order_keep_dev = wset;
+    ctx->left.order_pending = w; ctx->left.order_pending_sig = sig; ctx->left.order_tiles = tiles_painted;
+    ctx->hand.order_cnt_dev = tab.order_cnt; ctx->hand.order_keep_dev = wset;
     return FORMA_OK;
 }
 // the carry pre-pass as `cp` planned it
@@ -785,13 +772,13 @@ PaintInputs paint_inputs(forma_hip_ctx* ctx, const FrameTables& tab, DevCount jc
 
 // stage 4 on ctx->sorted (n segments): runs + carry pre-pass + per-tile painter -> ctx->image
 // bound_j != 0: asynchronous — the run count stays on the device (info->n_runs), buffers are provisioned for bound_j runs.
-int run_paint(forma_hip_ctx* ctx, DevCount nc, const PaintArgs& a, bool timing, uint32_t bound_j = 0) {
+int run_paint(forma_hip_ctx* ctx, DevCount nc, const PaintArgs& a, bool timing, uint32_t bound_j = 0, FrameMode mode = {}) {
     const size_t n = nc.bound;
+    ctx->left = Enqueued();                               // (the frame before this one is verified and delivered, or given up)
     // set_styles and set_images are separate calls: the image a texture style names is checked where both are known
     if (ctx->scene.any_texture && ctx->scene.max_image_index >= ctx->scene.n_images) return fail(ctx, FORMA_E_ARG, "texture style names an image that was not uploaded");
     const uint32_t tiles_w = a.tiles_w(), tiles_h = a.tiles_h();
     ctx->img_w = a.width; ctx->img_h = a.height;
-    ctx->chain_rows = nullptr; ctx->n_chain_rows = 0;
     int rc; PaintTarget tg;
     if ((rc = paint_target(ctx, a, &tg))) return rc;
     HIPCHECK(ctx->row_tab.ensure(frame_tables(nullptr, tiles_w, tiles_h).total_words * 4));
@@ -799,15 +786,14 @@ int run_paint(forma_hip_ctx* ctx, DevCount nc, const PaintArgs& a, bool timing, 
     HIPCHECK(ctx->blk_edge.ensure(runs_blocks(std::max<size_t>(n, 1)) * sizeof(BlkEdge)));
     HIPCHECK(ctx->runs_scratch.ensure(runs_scratch_words(std::max<size_t>(n, 1)) * 4));
     stage_begin(ctx, ST_CARRY, timing);
-    const bool tables_zero = ctx->pz.tab_p == ctx->row_tab.p && ctx->pz.tab_words >= tab.zero_words;
-    ctx->pz.tab_p = nullptr;
+    const bool tables_zero = take(ctx->hand.pz.tab).covers(ctx->row_tab.p, tab.zero_words);
     CarryPlan cp = plan_carry(ctx, a, n, bound_j);
     DevCount jc; uint32_t J;
     if ((rc = number_runs(ctx, nc, a, tab, bound_j, tables_zero, &cp, &jc, &J))) return rc;
     SpanGroups groups; const uint64_t* sorted_keys;
     if ((rc = provision_spans(ctx, jc, tiles_w, tiles_h, cp.local_sort, &groups, &sorted_keys))) return rc;
     if (jc.bound > 0) settle_carry(ctx, &cp, bound_j);
-    ctx->image_sent = false;
+    ctx->guess.plan = cp; ctx->guess.read_back_free = bound_j != 0;      // (a frame without runs: the plan as plan_carry made it)
     // (no runs: the carry pre-pass does not run, the zeroed tables say "no spans")
     PaintParams P = paint_params(ctx, a, tg.clear_unchanged, jc.bound > 0 ? cp.n_slices : 1u, cp.chain || cp.blk ? &tab : nullptr);
     const uint32_t tiles_painted = (P.crop_y1 > P.crop_y0 ? P.crop_y1 - P.crop_y0 : 0u) * tiles_w;
@@ -815,8 +801,8 @@ int run_paint(forma_hip_ctx* ctx, DevCount nc, const PaintArgs& a, bool timing, 
     const bool quads = paint_by_quads(ctx, a.cache_id, cp.chain ? bound_j : jc.bound, tiles_painted);   // (k_paint_quad ignores order_*)
     // a frame that leaves in bands paints in several launches: no heavy-first order across them
     // (split_plan runs before launch_deep is known, which may drop the split below: ADVICE.md, third finding)
-    const int split_n = split_plan(ctx, a, P, bound_j, timing);
-    if ((rc = heavy_order(ctx, a, bound_j, jc, tab, tiles_painted, strips, quads, split_n, &P))) return rc;
+    const int split_n = split_plan(ctx, a, P, bound_j, timing, mode.may_split);
+    if ((rc = heavy_order(ctx, a, bound_j, jc, tab, tiles_painted, strips, quads, split_n, mode.tail, &P))) return rc;
     // the (empty) k_paint_deep launch costs ~5 us of every frame: a read-back-free frame without a cache skips it when the
     // last verified frame had no deep tile; a tile that needs it then voids the frame (re-run in full)
     const bool launch_deep = !(bound_j != 0 && a.cache_id < 0 && ctx->learned.pred_no_deep);
@@ -825,28 +811,28 @@ int run_paint(forma_hip_ctx* ctx, DevCount nc, const PaintArgs& a, bool timing, 
     stage_begin(ctx, ST_PAINT, timing);
     // the painter in bands of tile rows, an event behind each (enqueue_own sends their pixels out behind those) — or as one band
     const int bands = split_n > 1 && !launch_deep ? split_n : 1;
-    ctx->split_n = 0;
-    ctx->split_row[0] = P.crop_y0; ctx->split_row[bands] = P.crop_y1;
+    uint32_t* const split_row = ctx->left.split_row;
+    split_row[0] = P.crop_y0; split_row[bands] = P.crop_y1;
     if (bands > 1) {
         const uint32_t rows = P.crop_y1 - P.crop_y0;
-        for (int k = 1; k < bands; k++) ctx->split_row[k] = P.crop_y0 + (uint32_t)((uint64_t)rows * (uint32_t)k / (uint32_t)bands);
+        for (int k = 1; k < bands; k++) split_row[k] = P.crop_y0 + (uint32_t)((uint64_t)rows * (uint32_t)k / (uint32_t)bands);
         // the policy's two bands: the first a quarter of the rows (split_first) — its copy must last until the rest is painted, or
         // the link idles between the two (10 %: slower than one launch; 22-30 %: the plateau; profiles/r06_experiments.txt, r8g)
-        if (bands == 2) ctx->split_row[1] = P.crop_y0 + std::min(std::max(rows * (uint32_t)ctx->dbg.split_first / 100u, 1u), rows - 1u);
+        if (bands == 2) split_row[1] = P.crop_y0 + std::min(std::max(rows * (uint32_t)ctx->dbg.split_first / 100u, 1u), rows - 1u);
     }
     const PaintInputs in = paint_inputs(ctx, tab, jc, tg.tc);
     for (int k = 0; k < bands; k++) {
         PaintParams Pk = P;
-        Pk.crop_y0 = ctx->split_row[k]; Pk.crop_y1 = ctx->split_row[k + 1];
+        Pk.crop_y0 = split_row[k]; Pk.crop_y1 = split_row[k + 1];
         launch_paint(ctx->stream, Pk, in, tab, groups, launch_deep, strips, quads, ctx->n_cus, a.fmt);
         if (bands > 1) HIPCHECK(hipEventRecord(ctx->split_ev[k], ctx->stream));
     }
-    if (bands > 1) ctx->split_n = bands;
+    if (bands > 1) ctx->left.split_n = bands;
     stage_end(ctx, ST_PAINT, timing);
     ctx->last_runs = J; ctx->last_entries = 0;
     HIPCHECK(hipGetLastError());
     // what a later launch_paint_huge needs (tiles deeper than the painter's LDS lists: finish_paint)
-    ctx->huge = forma_hip_ctx::HugeArgs{P, jc, tg.tc, a.fmt};
+    ctx->left.huge = Enqueued::HugeArgs{P, jc, tg.tc, a.fmt};
     return FORMA_OK;
 }
 
@@ -856,7 +842,7 @@ int run_paint(forma_hip_ctx* ctx, DevCount nc, const PaintArgs& a, bool timing, 
 // of the image is copied out.  Rare (thousands of layers in one 16 x 16 tile), so the extra round trip does not matter.
 int finish_paint(forma_hip_ctx* ctx, bool timing) {
     if (!(ctx->h_info->error & 8u)) return FORMA_OK;
-    const forma_hip_ctx::HugeArgs& h = ctx->huge;
+    const Enqueued::HugeArgs& h = ctx->left.huge;
     const FrameTables tab = frame_tables(ctx->row_tab.as<uint32_t>(), h.P.tiles_w, h.P.tiles_h);
     uint32_t n = 0;
     HIPCHECK(hipMemcpyAsync(&n, tab.over2_n, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -906,25 +892,24 @@ int copy_rows_out(forma_hip_ctx* ctx, hipStream_t s, uint8_t* dst, size_t stride
 // the bands of a split frame (run_paint): each leaves on copy_stream behind its painter launch's event.  Called when ALL of the
 // frame's kernels are enqueued — a copy into pageable memory blocks the host until it is done.
 int send_split_bands(forma_hip_ctx* ctx, uint8_t* dst, size_t stride, const PaintArgs& a) {
-    if (ctx->split_n < 2 || !dst) return FORMA_OK;
+    if (ctx->left.split_n < 2 || !dst) return FORMA_OK;
     const TileRect crop = crop_tiles(a);
     if (crop.x0 >= crop.x1) return FORMA_OK;
     const size_t px0 = (size_t)crop.x0 * 16, px1 = std::min<size_t>((size_t)crop.x1 * 16, a.width);
-    ctx->split_sent = true;
-    for (int k = 0; k < ctx->split_n; k++) {
-        const size_t py0 = (size_t)ctx->split_row[k] * 16, py1 = std::min<size_t>((size_t)ctx->split_row[k + 1] * 16, a.height);
+    ctx->left.split_sent = true;
+    for (int k = 0; k < ctx->left.split_n; k++) {
+        const size_t py0 = (size_t)ctx->left.split_row[k] * 16, py1 = std::min<size_t>((size_t)ctx->left.split_row[k + 1] * 16, a.height);
         HIPCHECK(hipStreamWaitEvent(ctx->copy_stream, ctx->split_ev[k], 0));
         if (py0 >= py1) continue;
         const int rc = copy_rows_out(ctx, ctx->copy_stream, dst, stride, px0, px1, py0, py1, a.width);
         if (rc) return rc;
     }
-    ctx->image_sent = true;
+    ctx->left.image_sent = true;
     return FORMA_OK;
 }
 // ... and nothing touches `dst` (or repaints the device image) before they have landed
 int settle_split(forma_hip_ctx* ctx) {
-    if (!ctx->split_sent) return FORMA_OK;
-    ctx->split_sent = false;
+    if (!take(ctx->left.split_sent)) return FORMA_OK;
     HIPCHECK(hipStreamSynchronize(ctx->copy_stream));
     return FORMA_OK;
 }
@@ -1023,9 +1008,9 @@ int finish_frame(forma_hip_ctx* ctx, forma_timings_t* t, bool have_info = false)
         const uint32_t* r = ctx->h_info->tile_range;
         ctx->learned.pred_range = KeyRange{~r[0], r[1], ~r[2], r[3], true};
     }
-    if (!ctx->h_info->plan_bad) ctx->learned.pred_row_spans = ctx->h_info->n_spans / ctx->cur_rows_painted;
+    if (!ctx->h_info->plan_bad) ctx->learned.pred_row_spans = ctx->h_info->n_spans / ctx->guess.plan.rows_painted;
     if (!ctx->h_info->plan_bad && ctx->h_info->n_slices) ctx->learned.pred_slice_len = std::max(ctx->h_info->n_segments / ctx->h_info->n_slices, 1u);
-    if (!ctx->h_info->plan_bad) { ctx->learned.pred_max_slice = ctx->h_info->max_slice_runs; ctx->learned.pred_slice_n = ctx->cur_slices; ctx->learned.pred_slice_small = ctx->cur_small; ctx->learned.pred_slice_half = ctx->cur_half; }
+    if (!ctx->h_info->plan_bad) { ctx->learned.pred_max_slice = ctx->h_info->max_slice_runs; ctx->learned.pred_slice_n = ctx->guess.plan.n_slices; ctx->learned.pred_slice_small = ctx->guess.plan.small; ctx->learned.pred_slice_half = ctx->guess.plan.half; }
     if ((ctx->h_info->error & ~24u) == 1u)                   // (bit 0: k_carry_rows met a run of a layer without a style)
         return fail(ctx, FORMA_E_ARG, "a geometry entry names an order that has no style (forma_hip_set_styles: offset FORMA_NONE or beyond the table)");
     if (ctx->h_info->error & ~24u) return fail(ctx, FORMA_E_INTERNAL, "device-side invariant violated");
@@ -1066,14 +1051,13 @@ int finish_frame(forma_hip_ctx* ctx, forma_timings_t* t, bool have_info = false)
 void clear_stage_flags(forma_hip_ctx* ctx) {
     for (int s = 0; s < ST_COUNT; s++) ctx->stage_used[s] = false;
     ctx->kt.n = 0; ctx->kt.dropped = 0; g_ktimer = nullptr;
-    ctx->order_cnt_dev = nullptr; ctx->order_keep_dev = nullptr;       // (a frame that never reached its k_frame_tail)
 }
 
 // How every frame ends once its kernels are on the stream: FrameInfo on the host, the over-deep tiles painted, the image in
 // caller memory (and landed there when the call returns), timings resolved, the clear colour remembered in the cache.
 //   info_on_host: k_frame_tail brought FrameInfo (a read-back-free frame, already waited for); else it is read back now.
 //   early_image:  the frame's image may have left before it was verified (a deferred frame into caller memory, a split frame's
-//                 bands: image_sent / split_sent) — own-geometry read-back-free frames only.
+//                 bands: Enqueued::image_sent / split_sent) — own-geometry read-back-free frames only.
 int deliver(forma_hip_ctx* ctx, const FrameRequest& r, bool info_on_host, bool early_image) {
     const PaintArgs a = r.paint();
     int rc;
@@ -1082,8 +1066,8 @@ int deliver(forma_hip_ctx* ctx, const FrameRequest& r, bool info_on_host, bool e
     //  is copied again)
     bool in_place = false, was_split = false;
     if (early_image) {
-        in_place = ctx->image_sent && !(ctx->h_info->error & 8u);
-        was_split = ctx->split_sent;
+        in_place = ctx->left.image_sent && !(ctx->h_info->error & 8u);
+        was_split = ctx->left.split_sent;
         if ((rc = settle_split(ctx))) return rc;           // (a split frame: its bands have landed — or land before the crop is copied again)
     }
     if ((rc = finish_paint(ctx, r.timing()))) return rc;
@@ -1377,7 +1361,7 @@ void forma_hip_destroy(forma_hip_ctx* ctx) {
     for (auto& r : ctx->registered) (void)hipHostUnregister(r.first);
     if (ctx->copy_stream) {
         (void)hipStreamSynchronize(ctx->copy_stream);
-        for (int k = 0; k < forma_hip_ctx::SPLIT_MAX; k++) if (ctx->split_ev[k]) (void)hipEventDestroy(ctx->split_ev[k]);
+        for (int k = 0; k < SPLIT_MAX; k++) if (ctx->split_ev[k]) (void)hipEventDestroy(ctx->split_ev[k]);
         (void)hipStreamDestroy(ctx->copy_stream);
     }
     if (ctx->wait_ev) (void)hipEventDestroy(ctx->wait_ev);
@@ -1873,7 +1857,7 @@ int forma_hip_sort(forma_hip_ctx* ctx, uint64_t* segments, size_t n, int digit_b
     ctx->seg_u_fused = false;
     ctx->live44 = host_live44(segments, n);
     ctx->layer_sorted = false;
-    ctx->pz = forma_hip_ctx::PreZero();
+    begin_stream(ctx);
     int rc = reset_info(ctx);
     if (rc) return rc;
     if ((rc = run_sort(ctx, ctx->seg_u.as<uint64_t>(), DevCount{nullptr, (uint32_t)n}, false, digit_bits))) return rc;
@@ -1892,7 +1876,7 @@ int forma_hip_paint(forma_hip_ctx* ctx, const uint64_t* sorted_segments, size_t 
     ENTER_STAGE(ctx);
     HIPCHECK(hipSetDevice(ctx->device));
     clear_stage_flags(ctx);
-    ctx->pz = forma_hip_ctx::PreZero();
+    begin_stream(ctx);
     if ((rc = reset_info(ctx))) return rc;
     HIPCHECK(ctx->seg_a.ensure((std::max<size_t>(n, 1) + SEG_PAD) * 8));
     if (n) HIPCHECK(hipMemcpyAsync(ctx->seg_a.p, sorted_segments, n * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -1944,30 +1928,24 @@ inline bool may_enqueue(const forma_hip_ctx* ctx) { return ctx->learned.pred_val
 
 // The front of the context's own geometry, read-back-free: N, J and the sort plan are predicted from the previous frame (bounds
 // with slack); device-side guards keep a wrong guess memory-safe.
-int enqueue_own_kernels(forma_hip_ctx* ctx, const PaintArgs& a, bool timing, uint32_t bN, uint32_t bJ) {
+int enqueue_own_kernels(forma_hip_ctx* ctx, const PaintArgs& a, bool timing, uint32_t bN, uint32_t bJ, FrameMode mode) {
     FrameInfo* dinfo = ctx->info.as<FrameInfo>();
     int rc;
     if ((rc = poison_frame_buffers(ctx))) return rc;
     // a frame of kernels only: what later stages need cleared is cleared by the first kernel, FrameInfo reaches the host
     // (and returns to its pristine state) through the last one
-    ZeroJobs Z; forma_hip_ctx::PreZero cleared;
+    ZeroJobs Z; PreZero cleared;
     if ((rc = plan_zero_jobs(ctx, a.width, a.height, bN, bN, &Z, &cleared))) return rc;
     if ((rc = run_rasterize_frame(ctx, a.width, a.height, timing, true, bN, &Z, &cleared, /*hist_too=*/true))) return rc;
-    if ((rc = run_sort(ctx, ctx->seg_u.as<uint64_t>(), DevCount{&dinfo->n_segments, bN}, timing))) return rc;
-    ctx->order_enable = true;                             // (this frame ends with k_frame_tail: the painters may leave their order lists)
-    rc = run_paint(ctx, DevCount{&dinfo->n_segments, bN}, a, timing, bJ);
-    ctx->order_enable = false;
-    if (rc) return rc;
+    if ((rc = run_sort(ctx, ctx->seg_u.as<uint64_t>(), DevCount{&dinfo->n_segments, bN}, timing, 0, nullptr, mode))) return rc;
+    if ((rc = run_paint(ctx, DevCount{&dinfo->n_segments, bN}, a, timing, bJ, mode))) return rc;
     return frame_tail(ctx, true, nullptr);
 }
 int enqueue_own(forma_hip_ctx* ctx, FrameRequest& r, bool* parked) {
     const PaintArgs a = r.paint();
     r.bN = ctx->learned.pred_N + ctx->learned.pred_N / 16 + 4096; r.bJ = ctx->learned.pred_J + ctx->learned.pred_J / 16 + 4096;
-    ctx->split_want = !parked && r.dst && !r.timing();    // (into caller memory and verified at once: the painter may run in bands, run_paint)
-    ctx->split_n = 0;
-    ctx->frame_has_dst = parked && r.dst;                 // (sort_workgroups: such a frame's digit passes keep the whole chip)
-    int rc = enqueue_own_kernels(ctx, a, r.timing(), r.bN, r.bJ);
-    ctx->split_want = false; ctx->frame_has_dst = false;
+    const FrameMode mode{/*tail=*/true, /*may_split=*/!parked && r.dst && !r.timing(), /*has_dst=*/parked && r.dst};
+    int rc = enqueue_own_kernels(ctx, a, r.timing(), r.bN, r.bJ, mode);
     if (rc) return rc;
     if (!parked) {
         if ((rc = send_split_bands(ctx, r.dst, r.stride, a))) (void)settle_split(ctx);
@@ -1978,7 +1956,7 @@ int enqueue_own(forma_hip_ctx* ctx, FrameRequest& r, bool* parked) {
         // the image leaves speculatively, in one piece behind the frame's kernels (verified at settle time; a void frame
         // is run again into `dst`): it crosses PCIe while the NEXT frames are rasterized, sorted and painted
         rc = copy_image_out(ctx, r.dst, r.stride, false, a);
-        ctx->image_sent = rc == FORMA_OK;
+        ctx->left.image_sent = rc == FORMA_OK;
     }
     return rc;
 }
@@ -2011,10 +1989,10 @@ int wait_frame_tail(forma_hip_ctx* ctx, bool timing) {
 
 // a verified frame's painters left their heaviest-first lists: they become the current set, and the threshold is steered
 void take_over_order(forma_hip_ctx* ctx) {
-    if (ctx->order_pending < 0) return;
-    ctx->learned.order_cur = ctx->order_pending; ctx->learned.order_sig = ctx->order_pending_sig; ctx->order_pending = -1;
+    if (ctx->left.order_pending < 0) return;
+    ctx->learned.order_cur = std::exchange(ctx->left.order_pending, -1); ctx->learned.order_sig = ctx->left.order_pending_sig;
     // steer the threshold: the heavy section should hold the few percent of the tiles that make the launch's tail
-    const uint32_t nh = ctx->h_info->n_heavy, nt = std::max(ctx->order_tiles, 1u);
+    const uint32_t nh = ctx->h_info->n_heavy, nt = std::max(ctx->left.order_tiles, 1u);
     if (nh * 16u > nt) ctx->learned.order_thr = std::min<uint32_t>(ctx->learned.order_thr + ctx->learned.order_thr / 4u, 1u << 24);        // > 6 %
     else if (nh * 50u < nt) ctx->learned.order_thr = std::max<uint32_t>(ctx->learned.order_thr - ctx->learned.order_thr / 5u, 1u << 12);     // < 2 %
     // ... of a scene that HAS a tail: a tile is heavy from twice the average on (sampled: FrameInfo::cost_*)
@@ -2031,8 +2009,8 @@ void take_over_order(forma_hip_ctx* ctx) {
 // The verdict on a read-back-free frame whose FrameInfo has arrived.  FORMA_OK: its predictions held and are taken over.
 // FORMA_RETRY: a prediction failed, nothing of the frame may be used (it is run again synchronously, which re-learns
 // everything).  own_counts: the stream is the context's own geometry — N is checked against the bound it was rasterized under
-// and taken over with the line count; the painters of such a frame may have left their order lists (order_enable is raised by
-// enqueue_own_kernels only) and a void frame drops them; its bands may be on their way to `dst`, which the re-run writes again.
+// and taken over with the line count; the painters of such a frame may have left their order lists (FrameMode::tail: enqueue_own
+// only) and a void frame drops them; its bands may be on their way to `dst`, which the re-run writes again.
 // A received stream's N is bounded by the exchange plan (exchange_overflow, verify_frame) and predicts nothing here.
 int judge_frame(forma_hip_ctx* ctx, const FrameRequest& r, bool own_counts) {
     const FrameInfo& fi = *ctx->h_info;
@@ -2046,11 +2024,12 @@ int judge_frame(forma_hip_ctx* ctx, const FrameRequest& r, bool own_counts) {
         return FORMA_OK;
     }
     if (own_counts) { const int src = settle_split(ctx); if (src) return src; }
-    if (ctx->small_tried && fi.plan_bad) ctx->learned.small_banned = true;   // (one cause of plan_bad: a slice beyond the small variant)
-    if (ctx->covl_tried && fi.plan_bad) ctx->learned.covl_banned = true;     // (another: a row beyond the COVL carry variant's LDS)
-    if (ctx->plan_biased && fi.plan_bad) ban_bias(ctx);              // (another: a key outside the span the digits were planned for)
+    const Guesses& g = ctx->guess;
+    if (g.plan.small && g.read_back_free && fi.plan_bad) ctx->learned.small_banned = true;   // (one cause of plan_bad: a slice beyond the small variant)
+    if (g.plan.covl && g.read_back_free && fi.plan_bad) ctx->learned.covl_banned = true;     // (another: a row beyond the COVL carry variant's LDS)
+    if (g.plan_biased && fi.plan_bad) ban_bias(ctx);              // (another: a key outside the span the digits were planned for)
     ctx->learned.pred_counts_valid = false;
-    if (own_counts) { ctx->learned.order_cur = -1; ctx->order_pending = -1; }
+    if (own_counts) { ctx->learned.order_cur = -1; ctx->left.order_pending = -1; }
     clear_stage_flags(ctx);
     return FORMA_RETRY;
 }
@@ -2361,7 +2340,7 @@ int forma_hip_trim(forma_hip_ctx* ctx) {
     for (forma_hip_ctx* c : frame_slots(ctx)) {
         HIPCHECK(hipSetDevice(c->device));
         HIPCHECK(hipStreamSynchronize(c->stream));
-        c->learned.order_cur = -1; c->order_pending = -1; c->order_cnt_dev = nullptr; c->order_keep_dev = nullptr;
+        c->learned.order_cur = -1; c->hand = HandOffs();   // (every stream has ended, and the buffers the hand-offs point into go)
         size_t freed = 0;
         for (const auto& bufs : {c->frame_bufs(), c->trimmed_bufs()})
             for (DevBuf* b : bufs) { if (!b->borrowed) freed += b->cap; b->release(); }
@@ -2375,7 +2354,6 @@ int forma_hip_trim(forma_hip_ctx* ctx) {
         c->h_stage.release();                             // (pinned: a whole 4K image after a cache frame)
         c->sorted = nullptr; c->n_seg = 0; c->have_unsorted = false;
         c->cur_image = nullptr; c->img_w = 0; c->img_h = 0;
-        c->pending_masks = PendingMasks{nullptr, 0u};
         c->last_written = 0;
         clear_stage_flags(c);
     }
@@ -2543,20 +2521,19 @@ int forma_hip_sort_paint_frame(forma_hip_ctx* ctx, size_t n, uint8_t* dst, uint3
     HIPCHECK(hipSetDevice(ctx->device));
     const bool timing = timings != nullptr;
     clear_stage_flags(ctx);
-    ctx->pz = forma_hip_ctx::PreZero();
+    begin_stream(ctx);
     if ((rc = reset_info(ctx))) return rc;
     // the received stream lives in seg_b: move it to seg_u (the sort's read-only input) so a/b can ping-pong
     HIPCHECK(ctx->seg_u.ensure((std::max<size_t>(n, 1) + SEG_PAD) * 8));
     if (n) HIPCHECK(hipMemcpyAsync(ctx->seg_u.p, ctx->seg_b.p, n * 8, hipMemcpyDeviceToDevice, ctx->stream));
     ctx->n_seg = n; ctx->have_unsorted = true;
     ctx->live44 = 0xFFFFFFFFFFFull;                   // no varying-bit mask for a received stream: sort every digit
-    ctx->layer_sorted = false; ctx->speculated = false; // slices that are layer-sorted need not concatenate to a layer-sorted stream
+    ctx->layer_sorted = false;                        // slices that are layer-sorted need not concatenate to a layer-sorted stream
     if ((rc = run_sort(ctx, ctx->seg_u.as<uint64_t>(), DevCount{nullptr, (uint32_t)n}, timing))) return rc;
     const FrameRequest r(dst, width, height, stride_bytes, channels, clear_color, crop_or_null, -1, timings);
     if ((rc = run_paint(ctx, DevCount{nullptr, (uint32_t)n}, r.paint(), timing))) return rc;
     return deliver(ctx, r, false, false);
 }
-
 
 // ---- multi-GPU, exchange layout: every rank rasterizes 1/G of the LINES, pixel segments travel to the rank
 //      that owns their tile row (ONE all-to-all of u64 payloads, driven by the host language on this context's stream),
@@ -2622,7 +2599,7 @@ int forma_hip_rasterize_bucket_frame(forma_hip_ctx* ctx, uint32_t width, uint32_
     if ((rc = poison_frame_buffers(ctx))) return rc;
     // read-back-free on both halves: this call's first kernel also clears what the owner's half of the frame
     // (forma_hip_gather_sort_paint_frame: sort scratch, tile tables, run chain for a band of n_ranks x capacity segments) expects
-    ZeroJobs Z; forma_hip_ctx::PreZero cleared;
+    ZeroJobs Z; PreZero cleared;
     const bool ahead = bN && may_enqueue(ctx);
     if (ahead && (rc = plan_zero_jobs(ctx, width, height, ctx->xbands.n * ctx->xcap, ctx->xbands.n * ctx->xcap, &Z, &cleared))) return rc;
     if ((rc = run_rasterize_frame(ctx, width, height, timing, false, bN, ahead ? &Z : nullptr, ahead ? &cleared : nullptr))) return rc;
@@ -2673,8 +2650,10 @@ int enqueue_received(forma_hip_ctx* ctx, FrameRequest& r, bool* parked) {
     const uint64_t* recv = self ? ctx->xsend.as<uint64_t>() : ctx->xrecv.as<uint64_t>();
     FrameInfo* dinfo = ctx->info.as<FrameInfo>();
     int rc;
+    // (no begin_stream: the stream began in forma_hip_rasterize_bucket_frame, and what that call's first kernel cleared for this
+    //  one — HandOffs::pz — has to survive between the two API calls)
     r.bJ = ctx->learned.pred_J + ctx->learned.pred_J / 16 + 4096;
-    ctx->live44 = ctx->learned.pred_live44; ctx->layer_sorted = ctx->learned.pred_layer_sorted; ctx->speculated = true;
+    ctx->live44 = ctx->learned.pred_live44; ctx->layer_sorted = ctx->learned.pred_layer_sorted; ctx->guess.speculated = true;
     uint64_t live = ctx->live44;
     if (ctx->layer_sorted) live &= ~0x1FFFFFull;
     // The received buckets are sorted where they lie: the histogram kernel and the first digit pass read the rank-major
@@ -2685,12 +2664,12 @@ int enqueue_received(forma_hip_ctx* ctx, FrameRequest& r, bool* parked) {
         ctx->have_unsorted = false; ctx->n_lines = 0;
         const ChunkedSrc C{recv, G, ctx->xcap, ctx->xmask.as<uint32_t>()};
         if ((rc = run_sort(ctx, recv, DevCount{&dinfo->n_segments, bound}, timing, 0, &C))) return rc;
-        ctx->pending_masks = PendingMasks{ctx->xmask.as<uint32_t>(), sort_hist_blocks(bound)};
+        ctx->hand.pending_masks = PendingMasks{ctx->xmask.as<uint32_t>(), sort_hist_blocks(bound)};
     } else {
         if ((rc = reset_info(ctx))) return rc;
         stage_begin(ctx, ST_XCHG, timing);
         launch_gather_chunks(ctx->stream, recv, G, ctx->xcap, ctx->seg_u.as<uint64_t>(), dinfo, ctx->xmask.as<uint32_t>(), /*reduce_now=*/false);
-        ctx->pending_masks = PendingMasks{ctx->xmask.as<uint32_t>(), (uint32_t)(gather_mask_words(G, ctx->xcap) / 8)};
+        ctx->hand.pending_masks = PendingMasks{ctx->xmask.as<uint32_t>(), (uint32_t)(gather_mask_words(G, ctx->xcap) / 8)};
         stage_end(ctx, ST_XCHG, timing);
         ctx->have_unsorted = true; ctx->n_lines = 0;
         if ((rc = run_sort(ctx, ctx->seg_u.as<uint64_t>(), DevCount{&dinfo->n_segments, bound}, timing))) return rc;
@@ -2708,11 +2687,10 @@ int produce_received(forma_hip_ctx* ctx, const FrameRequest& r, bool) {
     const uint64_t* recv = self ? ctx->xsend.as<uint64_t>() : ctx->xrecv.as<uint64_t>();
     FrameInfo* dinfo = ctx->info.as<FrameInfo>();
     int rc;
-    ctx->pz = forma_hip_ctx::PreZero();                    // (nothing was cleared ahead of its stage — and nothing on this path ever is)
+    begin_stream(ctx);                                     // (nothing was cleared ahead of its stage — and nothing on this path ever is)
     if ((rc = reset_info(ctx))) return rc;
     stage_begin(ctx, ST_XCHG, timing);
     launch_gather_chunks(ctx->stream, recv, G, ctx->xcap, ctx->seg_u.as<uint64_t>(), dinfo, ctx->xmask.as<uint32_t>(), /*reduce_now=*/true);
-    ctx->pending_masks = PendingMasks{nullptr, 0u};
     stage_end(ctx, ST_XCHG, timing);
     ctx->have_unsorted = true; ctx->n_lines = 0;
     if ((rc = read_info(ctx))) return rc;
@@ -2721,7 +2699,7 @@ int produce_received(forma_hip_ctx* ctx, const FrameRequest& r, bool) {
     const uint64_t k_or = (uint64_t)ctx->h_info->key_or | ((uint64_t)ctx->h_info->key_or_hi << 32);
     const uint64_t k_and = (uint64_t)ctx->h_info->key_and | ((uint64_t)ctx->h_info->key_and_hi << 32);
     ctx->live44 = ctx->n_seg ? ((k_or ^ k_and) & 0xFFFFFFFFFFFull) : 0;
-    ctx->layer_sorted = ctx->h_info->layer_unsorted == 0; ctx->speculated = false;
+    ctx->layer_sorted = ctx->h_info->layer_unsorted == 0;
     return run_sort(ctx, ctx->seg_u.as<uint64_t>(), DevCount{nullptr, (uint32_t)ctx->n_seg}, timing);
 }
 constexpr Front RECEIVED{enqueue_received, produce_received, true};

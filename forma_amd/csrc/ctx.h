@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 #include "common.h"
@@ -180,6 +181,58 @@ struct Learned {
     void bucket_canvas(uint32_t w, uint32_t h) { if (w != xpred_w || h != xpred_h) { xpred_valid = false; xpred_w = w; xpred_h = h; } }
 };
 
+// ---- the frame being enqueued right now: what belongs to it, by lifetime ("The context's state by owner") ----
+// 1. An argument of ONE CALL: what enqueue_own knows about its frame, by value down to run_sort (sort_workgroups) and run_paint
+//    (heavy_order, split_plan).  Default: every other caller (run_sync, enqueue_received, the stage entry points).
+struct FrameMode {
+    bool tail = false;                      // the frame ends with k_frame_tail: its painters may leave their order lists (heavy_order)
+    bool may_split = false;                 // into caller memory and verified at once: the painter may run in bands (split_plan)
+    bool has_dst = false;                   // a parked frame whose image leaves behind its kernels: its digit passes keep the whole chip (sort_workgroups)
+};
+// How the frame's runs are numbered (launch_runs) and which carry kernel orders them (launch_carry_rows): plan_carry, settle_carry
+struct CarryPlan {
+    bool local_sort = false;                // the rows' runs are ordered inside k_carry_rows (else by a global radix sort)
+    bool chain = false, chain_zero = false, blk = false;   // numbered per tile row (its status words cleared by the frame's first kernel) / per 2 048-segment tile
+    uint32_t rows_painted = 1, n_slices = 1;               // tile rows the carry pre-pass visits, its workgroups per row
+    bool small = false, half = false, covl = false;        // the carry kernel's variant
+};
+// 2. The frame's GUESSES, written while it is enqueued and read back by its verdict
+struct Guesses {
+    bool speculated = false;                // the sort is planned from learned.pred_live44 / pred_layer_sorted (run_rasterize_frame, enqueue_received) — run_sort, number_runs, verify_speculation
+    bool plan_biased = false;               // ... and leans on learned.pred_range (run_sort) — judge_frame: a void frame bans the bias
+    CarryPlan plan;                         // the carry plan as run_paint settled it — judge_frame bans .small / .covl of a void frame, finish_frame
+    bool read_back_free = false;            //   learns .rows_painted, .n_slices, .small, .half; ... and whether that frame was enqueued (bound_j != 0)
+};
+// 3. HAND-OFFS from one stage of a stream to a later one.  begin_stream (api.cpp) resets them all: "nothing handed over"; the stage
+//    named first produces, the one named last TAKES — nobody else clears
+template <class T> inline T take(T& x) { return std::exchange(x, T{}); }
+struct Cleared {                            // words the frame's FIRST kernel cleared on behalf of a later stage (ZeroJobs, common.h)
+    const void* p = nullptr; size_t words = 0;
+    bool covers(const void* q, size_t n) const { return p == q && words >= n; }    // (else the stage clears for itself)
+};
+struct PreZero { Cleared sort, tab, chain, slice; };
+struct HandOffs {
+    PreZero pz;                             // plan_zero_jobs, through run_rasterize_frame — .sort: run_sort, .tab: run_paint, .chain: plan_carry (.slice is only read)
+    bool ras_hist_on = false, ras_fused = false;   // the rasterizer counted the digits of ras_plan into the sort's histograms (RasHist) / and wrote its blocks
+    SortPlan ras_plan{};                           //   partitioned by that plan's first digit (SliceSrc): run_rasterize_frame — run_sort, if its plan is the same
+    const uint32_t* sort_range = nullptr; uint32_t sort_range_n = 0;   // run_sort: the tile-field spans it leaves behind, a record per k_sort_hist workgroup — number_runs
+    PendingMasks pending_masks{nullptr, 0u, 0u};   // key masks per workgroup that nobody has combined (run_rasterize_frame, enqueue_received) — number_runs
+    const uint32_t* chain_rows = nullptr; uint32_t n_chain_rows = 0;   // number_runs: runs numbered per tile row or tile, the row counts — frame_tail sums them
+    const uint32_t* order_cnt_dev = nullptr; uint32_t* order_keep_dev = nullptr;   // heavy_order: the order counts and where they are kept — frame_tail copies
+};
+// 4. What run_paint's frame LEFT BEHIND for its verification and delivery: reset as a whole when run_paint starts.  Every member is
+//    dead by then — its readers run between this frame's run_paint and its delivery — and split_sent is false: every path from
+//    send_split_bands to the next frame passes settle_split (enqueue_own, judge_frame, deliver), a failed wait for the stream aside
+constexpr int SPLIT_MAX = 8;
+struct Enqueued {
+    int order_pending = -1;                 // heavy_order: the set of order lists this frame's painters write (-1: none) — take_over_order, a void frame (judge_frame)
+    Learned::OrderSig order_pending_sig; uint32_t order_tiles = 0;   // ... the canvas / crop they are for, the tiles painted (heavy_order) — take_over_order
+    int split_n = 0; uint32_t split_row[SPLIT_MAX + 1] = {};         // run_paint: bands of the painter (0: not split), their tile-row boundaries — send_split_bands
+    bool split_sent = false;                // send_split_bands: copies are on copy_stream, wait for it before `dst` is touched again — settle_split
+    bool image_sent = false;                // send_split_bands, enqueue_own: the image left behind the kernels, before the frame was verified — deliver
+    struct HugeArgs { PaintParams P; DevCount jc; TileCacheArgs tc; uint32_t fmt; } huge{};   // run_paint: what of the painter launch the context does not hold — finish_paint
+};
+
 struct forma_hip_ctx {
     int device = 0;
     uint32_t n_cus = 256;                   // hipDeviceProp_t::multiProcessorCount of `device` (MI355X: 256)
@@ -219,26 +272,14 @@ struct forma_hip_ctx {
     DevBuf run_lt;                  // one word per run: layer16 | open | tile_x + 1 (RunStyle, common.h)
     DevBuf rec_sp, run_lt_sp, row_sp;       // launch_runs' BLOCKS numbering (BlkRuns, common.h): records and digests indexed like the segments (N entries)
     DevBuf grp_tab, grp_list;       // span group lists (SpanGroups, common.h): table per (row, slice, group) and the entry pool
-    uint32_t cur_rows_painted = 1;
     // lines
     DevBuf l_order, l_x0, l_y0, l_dx, l_dy, l_a, l_b, l_c, l_d, l_len, scan_tmp;   // parity entry points only
     DevBuf cl_idx, cl_start, block_first, prep_scratch;                              // frame path: compacted line table
-    // carry pre-pass: slices per tile row and the LDS variant (api.cpp run_paint)
-    uint32_t cur_slices = 1;
     // the painters' heaviest-first order (PaintParams::order_*): two sets of {counts, lists}; a read-back-free frame reads the set
     // the last verified frame of the same canvas / crop wrote and writes the other one
     DevBuf order_buf;
-    Learned::OrderSig order_pending_sig;
-    uint32_t order_tiles = 0;                     // tiles of the pending frame
-    int order_pending = -1;                       // set this frame's painter writes (-1: none)
-    bool order_enable = false;                    // set by the caller of run_paint for frames that end with k_frame_tail
-    const uint32_t* order_cnt_dev = nullptr; uint32_t* order_keep_dev = nullptr;   // what that k_frame_tail copies
-    bool cur_half = false;                    // the 512-lane variant of the small carry kernel (api.cpp run_paint)
-    bool cur_small = false, small_tried = false;
-    bool covl_tried = false;                // the COVL carry variant (rows' covers in LDS) was this read-back-free frame's guess
     DevBuf slice_buf;                       // fused first digit pass (SliceSrc): slice table, tiles' first slices, slice list
-    DevBuf ras_masks;                       // k_rasterize: key masks per workgroup (8 words), combined by k_reduce_masks
-    PendingMasks pending_masks{nullptr, 0u}; // ... or, on read-back-free frames, by k_runs_count
+    DevBuf ras_masks;                       // k_rasterize: key masks per workgroup (8 words), combined by k_reduce_masks or, on read-back-free frames, by k_runs_count
     size_t n_lines = 0, n_compact = 0;
     // segments
     DevBuf seg_u, seg_a, seg_b, sort_counters;
@@ -265,52 +306,34 @@ struct forma_hip_ctx {
     DevBuf cache_written;                   // one byte per tile: written this frame
     PinnedBuf h_written;                    // copy of cache_written
     PinnedBuf h_stage;                      // staging image for tile-granular copy-out (released by trim: a whole 4K image after a cache frame)
-    bool frame_has_dst = false;             // the frame being enqueued on this slot also copies its image out (forma_hip_render_enqueue)
-    bool image_sent = false;                // a deferred frame into caller memory: its image left behind the kernels, before the frame was verified
     // A synchronous frame into caller memory (one frame in flight, no cache): the painter runs as two launches (tests: up to SPLIT_MAX) over
     // bands of tile rows, each followed by an event; the bands' copies go out on `copy_stream` behind those events, so the image
     // crosses PCIe while the rest of it is still being painted (api.cpp: run_paint, send_split_bands).
-    static constexpr int SPLIT_MAX = 8;
     hipStream_t copy_stream = nullptr;      // created on first use
     hipEvent_t  split_ev[SPLIT_MAX] = {};
-    bool     split_want = false;            // set by enqueue_own around the frame's kernels: this frame may split
-    int      split_n = 0;                   // bands of the frame just enqueued (0: not split)
-    uint32_t split_row[SPLIT_MAX + 1] = {}; // tile-row boundaries of the bands
-    bool     split_sent = false;            // copies are on copy_stream: wait for it before `dst` is touched again
     std::vector<std::pair<void*, size_t>> registered;   // caller buffers pinned by forma_hip_register_buffer
     int cur_cache = -1;                     // cache of the frame in flight
     uint8_t* cur_image = nullptr;           // device image of the frame in flight / last frame
     bool image_external = false;            // ... is the caller's device target (forma_hip_render_device): forma_hip_read_image refuses it
     hipEvent_t wait_ev = nullptr;           // forma_hip_render_device's wait_stream: recorded there, waited for on the frame's stream
     Learned learned;                        // what verified frames taught this slot
-    bool speculated = false;                // this frame's sort was planned from learned.pred_live44 / pred_layer_sorted
-    bool plan_biased = false;               // this frame's plan leans on learned.pred_range
+    Guesses guess;                          // the frame being enqueued: what it guessed,
+    HandOffs hand;                          //   what its stages hand to one another,
+    Enqueued left;                          //   and what it leaves for its verification and delivery
     bool seg_u_fused = false; uint32_t fused_w = 0, fused_h = 0;   // seg_u holds a fused frame's partitioned blocks (restore_unsorted)
-    bool ras_fused = false;                 // ... and wrote its blocks partitioned by ras_plan's first digit (SliceSrc)
-    bool ras_hist_on = false; SortPlan ras_plan;     // the rasterizer of this frame counted the digits of ras_plan into the sort's histograms (RasHist)
-    const uint32_t* sort_range = nullptr;   // the tile-field spans the frame's sort leaves behind (k_runs_count folds them into FrameInfo) ...
-    uint32_t sort_range_n = 0;              // ... one record per k_sort_hist workgroup
     DevBuf info, records, rk_u, rk_a, rk_b, blk_edge, runs_scratch, row_tab, span_key, span_cov, image;
     uint32_t img_w = 0, img_h = 0;
     FrameInfo* h_info = nullptr;            // pinned
     uint32_t*  h_seq = nullptr;             // pinned (behind h_info): the number of the last read-back-free frame whose k_frame_tail has run
     uint32_t   tail_seq = 0;                // ... and of the last one enqueued
     bool info_clean = false;                // the device FrameInfo is pristine: the last frame ended with k_frame_tail (reset_info is then free)
-    // what this frame's FIRST kernel cleared on behalf of later stages (ZeroJobs, common.h): consumed by run_sort / run_paint,
-    // which clear the words themselves when the pointer or the size is not what they need
-    struct PreZero { const void* sort_p = nullptr; size_t sort_words = 0; const void* tab_p = nullptr; size_t tab_words = 0;
-                     const void* chain_p = nullptr; size_t chain_words = 0; const void* slice_p = nullptr; size_t slice_words = 0; } pz;
     ForMaDebug dbg;                         // FORMA_HIP_DEBUG as it stood when the context was created (a frame slot: its owner's) — the switches' one home
     // radix digit width: 0 = 8, or 9 where that saves a pass (default); 4 / 8 / 9 forced (digit_bits=)
     int digit_bits() const { return dbg.digit_bits == 4 || dbg.digit_bits == 8 || dbg.digit_bits == 9 ? dbg.digit_bits : 0; }
     // carry_slices=N: that many workgroups per tile row in the carry pre-pass (0: by policy)
     uint32_t force_slices() const { return dbg.carry_slices > 0 ? (uint32_t)std::min(dbg.carry_slices, (int)CR_MAX_SLICES_HOST) : 0u; }
-    const uint32_t* chain_rows = nullptr;   // this frame's runs were numbered per tile row (launch_runs' chain): its row counts, for the
-    uint32_t n_chain_rows = 0;              //   frame tail, which sums them into the host's n_runs
     uint32_t* h_rows = nullptr;             // pinned: runs per tile row (synchronous frames), 2049 words
-    // tiles deeper than the painter's LDS lists (finish_paint): what of the painter launch the context does not hold; the scratch lists
-    struct HugeArgs { PaintParams P; DevCount jc; TileCacheArgs tc; uint32_t fmt; } huge{};
-    DevBuf huge_offs, huge_key, huge_tmp, huge_flag;
+    DevBuf huge_offs, huge_key, huge_tmp, huge_flag;   // finish_paint: the scratch lists of tiles deeper than the painter's LDS lists (Enqueued::huge)
     // frames in flight inside ONE context (forma_hip_set_frames_in_flight): slots[0] is the context itself, the others are
     // full contexts (own stream, own per-frame buffers) that BORROW the scene buffers.  A device-resident, cache-less frame
     // is enqueued on the next slot and verified when that slot is needed again (or at any call that needs the result).
@@ -356,7 +379,6 @@ struct forma_hip_ctx {
     std::vector<DevBuf*> kept_bufs() { return {&info, &info_init, &cache_written, &xsend, &xrecv}; }
     std::vector<PinnedBuf*> pinned_bufs() { return {&h_written, &h_stage, &h_geo, &h_tab_stage}; }   // the growing page-locked ones
 };
-
 
 // the owner of the frame slots and every slot of it, the owner first (one frame in flight: the owner alone)
 inline std::vector<forma_hip_ctx*> frame_slots(forma_hip_ctx* o) { return o->slots.empty() ? std::vector<forma_hip_ctx*>{o} : o->slots; }

@@ -77,6 +77,11 @@ class KeepRangeT(C.Structure):
     _fields_ = [("first", C.c_uint64), ("count", C.c_uint64)]
 
 
+class StrokeRangeT(C.Structure):
+    _fields_ = [("first", C.c_uint64), ("count", C.c_uint64), ("half_width", C.c_float), ("miter_limit", C.c_float),
+                ("join", C.c_uint32), ("cap", C.c_uint32)]
+
+
 class CountersT(C.Structure):
     _fields_ = [("geometry_points", C.c_uint64), ("geometry_uploads", C.c_uint64), ("geometry_appends", C.c_uint64),
                 ("geometry_retains", C.c_uint64), ("geometry_bytes_h2d", C.c_uint64), ("geometry_bytes_d2h", C.c_uint64),
@@ -104,6 +109,7 @@ SYMBOLS = {
     "forma_hip_set_images": (_i, [_vp, _vp, _sz, _vp, _sz]),
     "forma_hip_flatten": (_i, [_vp, _vp, _vp, _vp]),
     "forma_hip_geometry_append": (_i, [_vp, _vp, _vp, _vp, _sz]),
+    "forma_hip_geometry_append_stroked": (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "forma_hip_geometry_retain": (_i, [_vp, _vp, _sz, _vp, _sz]),
     "forma_hip_read_geometry": (_i, [_vp, _vp, _vp, _vp, _sz, _vp]),
     "forma_hip_counters": (_i, [_vp, _vp]),

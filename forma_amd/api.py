@@ -16,6 +16,7 @@ fallback and no dependency on oracle/.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import struct
 import weakref
 from dataclasses import dataclass, field
@@ -59,6 +60,13 @@ def _host():
         L.forma_host_batch_points.argtypes = [vp]; L.forma_host_batch_points.restype = sz
         L.forma_host_batch_flatten.argtypes = [vp, vp, vp, vp, vp]; L.forma_host_batch_flatten.restype = C.c_int
         L.forma_host_batch_tables.argtypes = [vp, vp]
+        if hasattr(L, "forma_host_path_stroke"):          # (as below: absent in an older build)
+            L.forma_host_builder_open_contours.argtypes = [vp, C.c_int]
+            L.forma_host_close.argtypes = [vp]
+            L.forma_host_path_stroke.argtypes = [vp, f, f, C.c_uint32, C.c_uint32]; L.forma_host_path_stroke.restype = vp
+            L.forma_host_path_is_stroked.argtypes = [vp]; L.forma_host_path_is_stroked.restype = C.c_int
+            L.forma_host_batch_append_stroked.argtypes = [vp, vp, vp]; L.forma_host_batch_append_stroked.restype = C.c_int
+            L.forma_host_batch_strokes.argtypes = [vp]; L.forma_host_batch_strokes.restype = sz
         if hasattr(L, "forma_host_batch_append"):         # (absent in an older build loaded through FORMA_HIP_LIB: tools' A/B runs)
             L.forma_host_batch_append.argtypes = [vp, vp]; L.forma_host_batch_append.restype = C.c_int
         _host_bound = True
@@ -125,9 +133,37 @@ class GeomPresTransform:
 
 
 # ---- paths ----------------------------------------------------------------------------------------
+class StrokeJoin:
+    Bevel = 0; Miter = 1; Round = 2
+
+
+class StrokeCap:
+    Butt = 0; Square = 1; Round = 2
+
+
+@dataclass(frozen=True)
+class StrokeStyle:
+    """How `Path.stroke` outlines a path (no reference counterpart: forma only fills).  `width` is the full width, in the units
+    of the path as it is when it is stroked; a miter join whose 1 / cos(turn / 2) exceeds `miter_limit` becomes a bevel."""
+    width: float
+    join: int = StrokeJoin.Miter
+    cap: int = StrokeCap.Butt
+    miter_limit: float = 4.0
+
+    def __post_init__(self):
+        if not (math.isfinite(self.width) and 0.0 < self.width <= 131072.0):
+            raise ValueError("stroke width must be finite, > 0 and <= 131072")
+        if not (math.isfinite(self.miter_limit) and self.miter_limit >= 1.0):
+            raise ValueError("miter_limit must be finite and >= 1")
+        if self.join not in (0, 1, 2) or self.cap not in (0, 1, 2):
+            raise ValueError("unknown join or cap")
+
+
 class Path:
-    def __init__(self, handle):
+    def __init__(self, handle, stroke_of: Optional["Path"] = None, style: Optional[StrokeStyle] = None):
         self._h = handle
+        self._stroke_of = stroke_of          # a stroked path: the path it outlines ...
+        self.stroke_style = style            # ... and how
 
     def __del__(self):
         try:
@@ -135,15 +171,35 @@ class Path:
         except Exception:
             pass
 
+    def stroke(self, style: StrokeStyle) -> "Path":
+        """The outline of this path as a path of its own: inserted into a layer, its flattened points are expanded on the
+        device into closed pieces (bodies, joins, caps) whose union under FillRule.NonZero is the stroke — EvenOdd is wrong
+        for it.  Contours are closed only where the path closes them (`PathBuilder(open_contours=True)`, `close()`); dashes
+        do not exist; a contour without a line of non-zero length (a dot) draws nothing.  A stroked path is terminal:
+        transform first, then stroke."""
+        if self._stroke_of is not None:
+            raise ValueError("a stroked path cannot be stroked again")
+        h = _host().forma_host_path_stroke(self._h, float(style.width) * 0.5, float(style.miter_limit), int(style.join), int(style.cap))
+        return Path(h, stroke_of=self, style=style)
+
     def transform(self, t9: Sequence[float]) -> "Path":           # path.rs:725-771
+        if self._stroke_of is not None:
+            raise ValueError("a stroked path is terminal: transform the path first, then stroke it")
         t = np.ascontiguousarray(t9, np.float32)
         assert t.size == 9
         return Path(_host().forma_host_path_transform(self._h, t.ctypes.data))
 
 
 class PathBuilder:
-    def __init__(self):
+    def __init__(self, open_contours: bool = False):
+        """`open_contours`: neither `move_to` nor `build` closes a contour with an implicit line (the default does, as the
+        reference: a fill needs it); `close()` closes the current contour with a real line.  What a stroke wants."""
         self._h = _host().forma_host_builder_new()
+        if open_contours:
+            _host().forma_host_builder_open_contours(self._h, 1)
+
+    def close(self):
+        _host().forma_host_close(self._h); return self
 
     def __del__(self):
         try:
@@ -434,6 +490,10 @@ class Layer:
     def insert(self, path: Path) -> "Layer":                  # layer.rs:90-111
         n = _host().forma_host_path_points(path._h)
         lines = _host().forma_host_path_lines(path._h)        # ids that are Some: what SegmentBuffer::len counts
+        if path._stroke_of is not None:
+            # a stroke's pieces are counted on the device, not here: the garbage estimate of compact_geom takes the SOURCE path's
+            # lines instead.  That threshold is a heuristic; an undercount only delays a compaction.
+            lines = _host().forma_host_path_lines(path._stroke_of._h)
         self._shared.pushes.append((self.geom_id_, path, lines))
         self._shared.geom_id_to_order[self.geom_id_] = self.order
         if n:
@@ -749,8 +809,42 @@ class Renderer:
         return None
 
     # -- geometry store: flatten every live path in one HIP launch, keep the result resident on the device
+    def _append_pushes(self, pushes) -> List[int]:
+        """append pushes (geom_id, path, lines) to the device's store in order; returns the points each one added.  Filled pushes
+        that follow each other go in one call, their counts known on the host; a stroked push goes in a call of its own,
+        because only the device knows what its pieces come to (forma_hip_geometry_append_stroked's out_points_added)."""
+        H = _host()
+        counts: List[int] = []
+        run: list = []
+
+        def flush():
+            if run:
+                self._ctx.geometry_append_paths(run)
+                del run[:]
+        for p in pushes:
+            item = (p[1], self._slot_of.setdefault(p[0], len(self._slot_of)))
+            if p[1]._stroke_of is None:
+                run.append(item)
+                counts.append(int(H.forma_host_path_points(p[1]._h)))
+            else:
+                flush()
+                counts.append(int(self._ctx.geometry_append_paths([item])))
+        flush()
+        return counts
+
     def _upload_geometry(self, comp: Composition):
         sh = comp._shared
+        if any(p._stroke_of is not None for _, p, _ in sh.pushes):
+            # stroked pushes: their pieces exist on the device only, so the store is built there through appends and the host's
+            # copy is read back from it
+            self._ctx.set_geometry(np.zeros(0, np.float32), np.zeros(0, np.float32), np.zeros(0, np.uint32))
+            self._slot_of = {}
+            self._append_pushes(sh.pushes)
+            x, y, ls = self._ctx.read_geometry()
+            self.host_tables.update(x=x, y=y, line_slot=ls)
+            self._geom_version = sh.geometry_version
+            self._geom_owner = sh
+            return
         live = [(g, p) for g, p, _ in sh.pushes]      # garbage is kept until compact_geom drops it; its slots get order NONE
         slot_of: Dict[int, int] = {}
         H = _host()
@@ -813,13 +907,8 @@ class Renderer:
             return self._upload_resident(comp)
         new = sh.pushes[len(dev):]                        # the pure append: O(new pushes)
         if new:
-            H = _host()
-            items = []
-            for p in new:
-                items.append((p[1], self._slot_of.setdefault(p[0], len(self._slot_of))))
-            self._ctx.geometry_append_paths(items)
+            self._dev_points.extend(self._append_pushes(new))
             self._dev_pushes.extend(new)
-            self._dev_points.extend(int(H.forma_host_path_points(p[1]._h)) for p in new)
         self._geom_version = sh.geometry_version
 
     def _upload_resident(self, comp: Composition):
@@ -827,12 +916,8 @@ class Renderer:
         sh = comp._shared
         self._ctx.set_geometry(np.zeros(0, np.float32), np.zeros(0, np.float32), np.zeros(0, np.uint32))
         self._slot_of = {}
-        items = [(p[1], self._slot_of.setdefault(p[0], len(self._slot_of))) for p in sh.pushes]
-        if items:
-            self._ctx.geometry_append_paths(items)
-        H = _host()
+        self._dev_points = self._append_pushes(sh.pushes)
         self._dev_pushes = list(sh.pushes)
-        self._dev_points = [int(H.forma_host_path_points(p[1]._h)) for p in sh.pushes]
         self._dev_epoch = sh.pushes_epoch
         self._geom_version = sh.geometry_version
         self._geom_owner = sh

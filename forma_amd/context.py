@@ -169,20 +169,52 @@ class Context:
         self._check(self._L.forma_hip_geometry_append(self._h, C.byref(ft), _p(ls), ar, len(affines)))
         self.n_points += int(t["n_points"])
 
+    JOINS = {"bevel": 0, "miter": 1, "round": 2}
+    CAPS = {"butt": 0, "square": 1, "round": 2}
+
+    def geometry_append_stroked(self, t, line_slot, affines=(), strokes=()):
+        """forma_hip_geometry_append_stroked: as geometry_append, with strokes = [(first, count, half_width, miter_limit, join,
+        cap)] — ascending point ranges of whole contours whose points are replaced by the pieces of their stroke (join / cap: a
+        FORMA_JOIN_* / FORMA_CAP_* value or its name).  Returns the number of points the store grew by."""
+        from ._lib import AffineRangeT, StrokeRangeT
+        ft, keep = self._flatten_tables(t)
+        ls = np.ascontiguousarray(line_slot, np.uint32)
+        assert len(ls) == int(t["n_points"])
+        ar = (AffineRangeT * max(len(affines), 1))()
+        for i, (first, count, m) in enumerate(affines):
+            ar[i].first, ar[i].count = int(first), int(count)
+            ar[i].m[:] = [float(v) for v in m]
+        sr = (StrokeRangeT * max(len(strokes), 1))()
+        for i, (first, count, hw, limit, join, cap) in enumerate(strokes):
+            sr[i].first, sr[i].count, sr[i].half_width, sr[i].miter_limit = int(first), int(count), float(hw), float(limit)
+            sr[i].join = self.JOINS[join] if isinstance(join, str) else int(join)
+            sr[i].cap = self.CAPS[cap] if isinstance(cap, str) else int(cap)
+        added = C.c_size_t(0)
+        self._check(self._L.forma_hip_geometry_append_stroked(self._h, C.byref(ft), _p(ls), ar, len(affines), sr, len(strokes), C.byref(added)))
+        self.n_points += int(added.value)
+        return int(added.value)
+
     def geometry_append_paths(self, items):
         """SegmentBuffer::push_path for every (path, slot) of `items`, in order: the host builds the paths' work items
-        (forma_host_batch_append), the device flattens them into the tail of the store."""
+        (forma_host_batch_append), the device flattens them into the tail of the store — and expands the stroked ones
+        (`Path.stroke`) into their pieces there.  Returns the number of points the store grew by."""
         from .api import _host
         H = _host()
         batch = H.forma_host_batch_new()
         try:
             for path, slot in items:
                 H.forma_host_batch_add(batch, path._h, int(slot))
-            n = H.forma_host_batch_points(batch)
-            self._check(H.forma_host_batch_append(batch, self._h))
+            if H.forma_host_batch_strokes(batch):          # stroked paths: the device says what their pieces came to
+                added = C.c_size_t(0)
+                self._check(H.forma_host_batch_append_stroked(batch, self._h, C.byref(added)))
+                n = added.value
+            else:
+                n = H.forma_host_batch_points(batch)
+                self._check(H.forma_host_batch_append(batch, self._h))
         finally:
             H.forma_host_batch_free(batch)
         self.n_points += int(n)
+        return int(n)
 
     def geometry_retain(self, keep, slot_remap):
         """forma_hip_geometry_retain: keep = [(first point, count)] ascending and disjoint, slot_remap[old slot] = new slot or NONE"""

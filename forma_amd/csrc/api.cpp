@@ -3,7 +3,9 @@
 // oracle/.  Errors never unwind across the ABI: every entry point returns a FORMA_E_* code.
 #include <new>
 
+#include <cmath>
 #include "ctx.h"
+#include "stroke.h"
 
 #ifndef FORMA_ARCH
 #define FORMA_ARCH "gfx950"
@@ -1629,8 +1631,74 @@ void geometry_edited(forma_hip_ctx* ctx) {
 }
 }  // namespace
 
-int forma_hip_geometry_append(forma_hip_ctx* ctx, const forma_flatten_tables_t* t, const uint32_t* line_slot,
-                              const forma_affine_range_t* affines, size_t n_affines) {
+namespace {
+// the stroked tail of geometry_append: the staging block `h` holds the work items up to word `at`; the contour and style tables
+// follow them.  The points are flattened into scratch (k_flatten_store, base 0), counted and scanned; the total comes back in a
+// first wait and sizes the store; the emit pass writes the pieces behind the store's contents and the second wait is append's.
+// Nothing of the store is touched before the total is known to fit.
+int append_stroked(forma_hip_ctx* ctx, const forma_flatten_tables_t& dt, const uint32_t* d_slot, const uint32_t* d_aff, size_t n_affines,
+                   const uint32_t* line_slot, const forma_stroke_range_t* strokes, size_t n_strokes, size_t n_contours, size_t at,
+                   size_t* out_points_added) {
+    const size_t np = dt.n_points;
+    uint32_t* h = ctx->h_geo.as<uint32_t>();
+    const uint32_t* d = ctx->geo_blob.as<uint32_t>();
+    const uint32_t* d_contours = d + at;
+    for (size_t i = 0; i < n_strokes; i++) {
+        const uint64_t end = strokes[i].first + strokes[i].count;
+        uint64_t first = strokes[i].first;
+        for (uint64_t k = first; k < end; k++)
+            if (line_slot[k] == FORMA_NONE) { h[at] = (uint32_t)first; h[at + 1] = (uint32_t)k; h[at + 2] = (uint32_t)i; at += 3; first = k + 1; }
+    }
+    const uint32_t* d_styles = d + at;
+    for (size_t i = 0; i < n_strokes; i++) {
+        memcpy(h + at, &strokes[i].half_width, 4); memcpy(h + at + 1, &strokes[i].miter_limit, 4);
+        h[at + 2] = strokes[i].join; h[at + 3] = strokes[i].cap;
+        at += 4;
+    }
+    const size_t bytes = at * 4;
+    // scratch: x, y, slot and count per source point, a sum per workgroup, the total (8-byte aligned: np4 is even)
+    const size_t np4 = (np + 1) & ~(size_t)1, nb = stroke_blocks((uint32_t)np);
+    HIPCHECK(ctx->stroke_tmp.ensure((4 * np4 + ((nb + 1) & ~(size_t)1) + 2) * 4));
+    uint32_t* w = ctx->stroke_tmp.as<uint32_t>();
+    StrokeArgs S{};
+    S.sx = (const float*)w; S.sy = (const float*)(w + np4); S.sslot = w + 2 * np4; S.n_src = (uint32_t)np;
+    S.contours = d_contours; S.n_contours = (uint32_t)n_contours; S.styles = d_styles;
+    S.counts = w + 3 * np4; S.block_base = w + 4 * np4;
+    S.total = (unsigned long long*)(w + 4 * np4 + ((nb + 1) & ~(size_t)1));
+    HIPCHECK(hipMemcpyAsync(ctx->geo_blob.p, h, bytes, hipMemcpyHostToDevice, ctx->stream));
+    GeomAppend A{0u, (uint32_t)n_affines, d_aff, d_slot, (float*)w, (float*)(w + np4), w + 2 * np4};
+    launch_flatten_store(ctx->stream, &dt, A);
+    launch_stroke_count(ctx->stream, S);
+    HIPCHECK(hipGetLastError());
+    unsigned long long total = 0;
+    HIPCHECK(hipMemcpyAsync(h, S.total, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHECK(hipStreamSynchronize(ctx->stream));          // (the first wait: the total sizes the store)
+    memcpy(&total, h, 8);
+    const size_t n_old = ctx->scene.n_points;
+    if (total >= (1ull << 30) || n_old + total >= (1ull << 30)) return fail(ctx, FORMA_E_ARG, "too many points");
+    ctx->cnt.geometry_bytes_h2d += bytes;
+    if (total == 0) return FORMA_OK;                      // (nothing but contours without a line of non-zero length)
+    const size_t n_new = n_old + (size_t)total;
+    HIPCHECK(ctx->x.grow_keep(n_new * 4, n_old * 4, ctx->stream));
+    HIPCHECK(ctx->y.grow_keep(n_new * 4, n_old * 4, ctx->stream));
+    HIPCHECK(ctx->line_slot.grow_keep(n_new * 4, n_old * 4, ctx->stream));
+    S.base = (uint32_t)n_old; S.limit = (uint32_t)n_new;
+    S.x = ctx->x.as<float>(); S.y = ctx->y.as<float>(); S.slot = ctx->line_slot.as<uint32_t>();
+    launch_stroke_emit(ctx->stream, S);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(ctx->stream));
+    ctx->scene.n_points = n_new;
+    ctx->cnt.geometry_appends++;
+    geometry_edited(ctx);
+    if (out_points_added) *out_points_added = (size_t)total;
+    return FORMA_OK;
+}
+
+// forma_hip_geometry_append and _append_stroked: one body.  Without stroke ranges it is the plain append, step for step.
+int geometry_append(forma_hip_ctx* ctx, const forma_flatten_tables_t* t, const uint32_t* line_slot,
+                    const forma_affine_range_t* affines, size_t n_affines,
+                    const forma_stroke_range_t* strokes, size_t n_strokes, size_t* out_points_added) {
+    if (out_points_added) *out_points_added = 0;
     if (!ctx || !t) return fail(ctx, FORMA_E_ARG, "null flatten tables");
     const size_t np = t->n_points, nq = t->n_quads, ns = t->n_splines;
     if (np == 0) return FORMA_OK;
@@ -1647,14 +1715,37 @@ int forma_hip_geometry_append(forma_hip_ctx* ctx, const forma_flatten_tables_t* 
               return fail(ctx, FORMA_E_ARG, "affine ranges must be ascending, disjoint and inside the appended points");
           end = affines[i].first + affines[i].count;
       } }
-    if (ctx->multi) return multi_geometry_append(ctx, t, line_slot, affines, n_affines);
+    // stroke ranges: ascending, disjoint, inside the appended points, whole contours; a style the kernels can take.
+    // n_contours: the stroked contours, one table entry each
+    size_t n_contours = 0;
+    if (n_strokes) {
+        if (!strokes) return fail(ctx, FORMA_E_ARG, "null stroke ranges");
+        uint64_t end = 0;
+        for (size_t i = 0; i < n_strokes; i++) {
+            const forma_stroke_range_t& r = strokes[i];
+            if (r.first < end || r.count > np || r.first > np - r.count)
+                return fail(ctx, FORMA_E_ARG, "stroke ranges must be ascending, disjoint and inside the appended points");
+            end = r.first + r.count;
+            if (!(r.half_width > 0.0f) || !(r.half_width <= SK_MAX_HALF_WIDTH)) return fail(ctx, FORMA_E_ARG, "a stroke's half width must be finite, > 0 and <= 65536");
+            if (!(r.miter_limit >= 1.0f) || !std::isfinite(r.miter_limit)) return fail(ctx, FORMA_E_ARG, "a stroke's miter limit must be finite and >= 1");
+            if (r.join > FORMA_JOIN_ROUND || r.cap > FORMA_CAP_ROUND) return fail(ctx, FORMA_E_ARG, "unknown stroke join or cap");
+            if (!r.count) continue;
+            if ((r.first && line_slot[r.first - 1] != FORMA_NONE) || line_slot[end - 1] != FORMA_NONE)
+                return fail(ctx, FORMA_E_ARG, "a stroke range must begin at a contour start and end on a FORMA_NONE");
+            for (uint64_t k = r.first; k < end; k++) n_contours += line_slot[k] == FORMA_NONE ? 1 : 0;
+        }
+    }
+    if (ctx->multi)
+        return n_strokes ? multi_geometry_append_stroked(ctx, t, line_slot, affines, n_affines, strokes, n_strokes, out_points_added)
+                         : multi_geometry_append(ctx, t, line_slot, affines, n_affines);
     if (ctx->scene.n_points + np >= (1ull << 30)) return fail(ctx, FORMA_E_ARG, "too many points");
     HIPCHECK(hipSetDevice(ctx->device));
     int rc;
     if ((rc = scene_drain(ctx))) return rc;               // frames in flight still read the store (and it may move when it grows)
     // ONE packed block: 4 words per point (3 work items + the line slot), 16 per quad (3 x 3 control values + 7 scalars), 4 per
     // spline, 8 per affine range
-    const size_t words = 4 * np + (9 + 7) * nq + 4 * ns + 8 * n_affines;
+    // (a stroked append adds 3 per stroked contour and 4 per stroke range)
+    const size_t words = 4 * np + (9 + 7) * nq + 4 * ns + 8 * n_affines + 3 * n_contours + 4 * n_strokes;
     const size_t bytes = words * 4;
     HIPCHECK(ctx->h_geo.ensure(bytes, 4096, true));      // (one append's work items: grown geometrically, kept)
     HIPCHECK(ctx->geo_blob.ensure(bytes));
@@ -1682,6 +1773,7 @@ int forma_hip_geometry_append(forma_hip_ctx* ctx, const forma_flatten_tables_t* 
         memcpy(h + at + 2, affines[i].m, 24);
         at += 8;
     }
+    if (n_strokes) return append_stroked(ctx, dt, d_slot, d_aff, n_affines, line_slot, strokes, n_strokes, n_contours, at, out_points_added);
     // the store grows geometrically and keeps its contents
     const size_t n_old = ctx->scene.n_points, n_new = n_old + np;
     HIPCHECK(ctx->x.grow_keep(n_new * 4, n_old * 4, ctx->stream));
@@ -1695,7 +1787,19 @@ int forma_hip_geometry_append(forma_hip_ctx* ctx, const forma_flatten_tables_t* 
     ctx->scene.n_points = n_new;
     ctx->cnt.geometry_appends++; ctx->cnt.geometry_bytes_h2d += bytes;
     geometry_edited(ctx);
+    if (out_points_added) *out_points_added = np;
     return FORMA_OK;
+}
+}  // namespace
+
+int forma_hip_geometry_append(forma_hip_ctx* ctx, const forma_flatten_tables_t* t, const uint32_t* line_slot,
+                              const forma_affine_range_t* affines, size_t n_affines) {
+    return geometry_append(ctx, t, line_slot, affines, n_affines, nullptr, 0, nullptr);
+}
+int forma_hip_geometry_append_stroked(forma_hip_ctx* ctx, const forma_flatten_tables_t* t, const uint32_t* line_slot,
+                                      const forma_affine_range_t* affines, size_t n_affines,
+                                      const forma_stroke_range_t* strokes, size_t n_strokes, size_t* out_points_added) {
+    return geometry_append(ctx, t, line_slot, affines, n_affines, strokes, n_strokes, out_points_added);
 }
 
 int forma_hip_geometry_retain(forma_hip_ctx* ctx, const forma_keep_range_t* keep, size_t n_keep, const uint32_t* slot_remap, size_t n_slots) {

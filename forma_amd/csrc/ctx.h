@@ -249,6 +249,7 @@ struct forma_hip_ctx {
     DevBuf x_spare, y_spare, line_slot_spare;
     DevBuf geo_blob;                        // one append's work items / one retain's tables, as uploaded
     DevBuf geo_flag;                        // k_geom_retain: a stored slot beyond the remap table
+    DevBuf stroke_tmp;                      // a stroked append: its flattened source points, their output counts, the scan's sums and total
     PinnedBuf h_geo;                        // staging of geo_blob (grown geometrically, kept); its first word receives geo_flag
     // the layer table edited with frames in flight (forma_hip_update_geoms / _update_geoms_xf; api.cpp "layer-table edits").
     // The OWNER of the frame slots keeps the table on the host (h_tab: always, forma_hip_read_geoms answers from it) and, from
@@ -374,7 +375,7 @@ struct forma_hip_ctx {
         &huge_flag, &grp_tab, &grp_list, &run_lt, &rec_sp, &run_lt_sp, &row_sp, &pack_list, &pack_pix, &slice_buf}; }
     // released by trim, not refilled: parity line parameters, the scratch image (a cropped frame leaves the rest alone), exchange scratch, order lists
     std::vector<DevBuf*> trimmed_bufs() { return {&l_order, &l_x0, &l_y0, &l_dx, &l_dy, &l_a, &l_b, &l_c, &l_d, &l_len, &image, &xscratch, &xmask, &order_buf,
-        &x_spare, &y_spare, &line_slot_spare, &geo_blob, &geo_flag}; }
+        &x_spare, &y_spare, &line_slot_spare, &geo_blob, &geo_flag, &stroke_tmp}; }
     // kept by trim, like the scene: FrameInfo and its template, cache frames' written-tile flags, the exchange's buckets
     std::vector<DevBuf*> kept_bufs() { return {&info, &info_init, &cache_written, &xsend, &xrecv}; }
     std::vector<PinnedBuf*> pinned_bufs() { return {&h_written, &h_stage, &h_geo, &h_tab_stage}; }   // the growing page-locked ones
@@ -432,6 +433,9 @@ int  multi_update_geoms(forma_hip_ctx* ctx, const uint32_t* slots, const forma_g
 int  multi_update_geoms_xf(forma_hip_ctx* ctx, uint32_t first, uint32_t count, const float* xf);
 int  multi_geometry_append(forma_hip_ctx* ctx, const forma_flatten_tables_t* t, const uint32_t* line_slot,
                            const forma_affine_range_t* affines, size_t n_affines);
+int  multi_geometry_append_stroked(forma_hip_ctx* ctx, const forma_flatten_tables_t* t, const uint32_t* line_slot,
+                                   const forma_affine_range_t* affines, size_t n_affines,
+                                   const forma_stroke_range_t* strokes, size_t n_strokes, size_t* out_points_added);
 int  multi_geometry_retain(forma_hip_ctx* ctx, const forma_keep_range_t* keep, size_t n_keep, const uint32_t* slot_remap, size_t n_slots);
 int  multi_counters(forma_hip_ctx* ctx, forma_counters_t* out);
 int  multi_set_styles(forma_hip_ctx* ctx, const uint32_t* style_offsets, size_t n_orders, const uint32_t* style_words,

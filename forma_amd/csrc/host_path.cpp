@@ -190,9 +190,11 @@ struct Path::Data {
     std::vector<float> x{0.0f}, y{0.0f}, w{1.0f};
     std::vector<uint8_t> cmd{0};            // 0 Move, 1 Line, 2 Quad, 3 Cubic
     size_t open_index = 0;
+    bool implicit_close = true;             // PathBuilder::open_contours(true) clears it
     std::unique_ptr<FlattenPlan> plan;      // memoised `segments` (path.rs:617-654)
 
-    void close() {                          // path.rs:596-615
+    void close(bool explicit_close = false) {   // path.rs:596-615
+        if (!implicit_close && !explicit_close) return;
         size_t n = x.size();
         V2 a = project({x[n - 1], y[n - 1], w[n - 1]});
         V2 b = project({x[open_index], y[open_index], w[open_index]});
@@ -205,6 +207,8 @@ struct Path::Data {
 };
 
 PathBuilder::PathBuilder() : d_(std::make_shared<Path::Data>()) {}
+PathBuilder& PathBuilder::open_contours(bool on) { d_->implicit_close = !on; return *this; }
+PathBuilder& PathBuilder::close() { d_->close(true); return *this; }
 PathBuilder& PathBuilder::move_to(Point p) {                    // path.rs:783-810
     Path::Data& d = *d_;
     size_t n = d.x.size();
@@ -268,6 +272,7 @@ Path Path::transform(const float t[9]) const {
     Path p;
     p.d_ = std::make_shared<Data>();
     p.d_->x = d_->x; p.d_->y = d_->y; p.d_->w = d_->w; p.d_->cmd = d_->cmd; p.d_->open_index = d_->open_index;
+    p.d_->implicit_close = d_->implicit_close;
     for (size_t i = 0; i < p.d_->x.size(); i++) {
         float x = d_->x[i], y = d_->y[i], w = d_->w[i];
         p.d_->x[i] = fmaf(t[0], x, fmaf(t[1], y, t[2] * w));
@@ -302,6 +307,8 @@ void FlattenBatch::add(const Path& path, uint32_t slot) {
         Affine a; a.first = pbase; a.count = pl.point_commands.size(); std::memcpy(a.m, path.affine(), sizeof a.m);
         affines.push_back(a);
     }
+    if (path.has_stroke() && !pl.point_commands.empty())          // (whole contours: the path before ended on NONE, this one does)
+        strokes.push_back({pbase, pl.point_commands.size(), path.stroke_style()});
 }
 
 void FlattenBatch::tables(forma_flatten_tables_t* t) const {
@@ -337,6 +344,12 @@ void  forma_host_rat_quad_to(void* b, float ax, float ay, float bx, float by, fl
 void  forma_host_rat_cubic_to(void* b, float ax, float ay, float bx, float by, float cx, float cy, float w1, float w2) {
     ((PathBuilder*)b)->rat_cubic_to({ax, ay}, {bx, by}, {cx, cy}, w1, w2);
 }
+void  forma_host_builder_open_contours(void* b, int on) { ((PathBuilder*)b)->open_contours(on != 0); }
+void  forma_host_close(void* b) { ((PathBuilder*)b)->close(); }
+void* forma_host_path_stroke(void* p, float half_width, float miter_limit, uint32_t join, uint32_t cap) {
+    return new Path(((Path*)p)->stroke({half_width, miter_limit, join, cap}));
+}
+int   forma_host_path_is_stroked(void* p) { return ((Path*)p)->has_stroke() ? 1 : 0; }
 void* forma_host_build(void* b) { return new Path(((PathBuilder*)b)->build()); }
 void  forma_host_path_free(void* p) { delete (Path*)p; }
 void* forma_host_path_transform(void* p, const float* t9) { return new Path(((Path*)p)->transform(t9)); }
@@ -367,7 +380,9 @@ int forma_host_batch_flatten(void* b_, forma_hip_ctx* ctx, float* out_x, float* 
 }
 // stage 1 for the whole batch STRAIGHT INTO the tail of the context's geometry store (SegmentBuffer::push_path for every
 // path of the batch): work items, line slots and the paths' affine ranges go up in one block, nothing comes back
-int forma_host_batch_append(void* b_, forma_hip_ctx* ctx) {
+// a batch with stroked paths goes through forma_hip_geometry_append_stroked: their points become the strokes' pieces on the
+// device, and *out_points_added (may be NULL) says how many points the store grew by
+int forma_host_batch_append_stroked(void* b_, forma_hip_ctx* ctx, size_t* out_points_added) {
     FlattenBatch* b = (FlattenBatch*)b_;
     forma_flatten_tables_t t;
     b->tables(&t);
@@ -376,8 +391,19 @@ int forma_host_batch_append(void* b_, forma_hip_ctx* ctx) {
         ranges[i].first = b->affines[i].first; ranges[i].count = b->affines[i].count;
         std::memcpy(ranges[i].m, b->affines[i].m, sizeof ranges[i].m);
     }
-    return forma_hip_geometry_append(ctx, &t, b->line_slot.data(), ranges.data(), ranges.size());
+    if (b->strokes.empty()) {
+        if (out_points_added) *out_points_added = t.n_points;
+        return forma_hip_geometry_append(ctx, &t, b->line_slot.data(), ranges.data(), ranges.size());
+    }
+    std::vector<forma_stroke_range_t> sr(b->strokes.size());
+    for (size_t i = 0; i < sr.size(); i++) {
+        const FlattenBatch::StrokeRange& s = b->strokes[i];
+        sr[i] = {s.first, s.count, s.style.half_width, s.style.miter_limit, s.style.join, s.style.cap};
+    }
+    return forma_hip_geometry_append_stroked(ctx, &t, b->line_slot.data(), ranges.data(), ranges.size(), sr.data(), sr.size(), out_points_added);
 }
+int forma_host_batch_append(void* b_, forma_hip_ctx* ctx) { return forma_host_batch_append_stroked(b_, ctx, nullptr); }
+size_t forma_host_batch_strokes(void* b) { return ((FlattenBatch*)b)->strokes.size(); }
 // expose the work items (tests compare them with the oracle's flattener output through the kernel)
 void forma_host_batch_tables(void* b, forma_flatten_tables_t* t) { ((FlattenBatch*)b)->tables(t); }
 }

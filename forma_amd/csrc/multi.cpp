@@ -759,6 +759,16 @@ int multi_geometry_append(forma_hip_ctx* ctx, const forma_flatten_tables_t* t, c
     EACH_KID(fd_set_line_range(k, false, 0, 0));
     return FORMA_OK;
 }
+// (the devices hold the same store and stroke alike: the first one refuses first, and every device adds the same points)
+int multi_geometry_append_stroked(forma_hip_ctx* ctx, const forma_flatten_tables_t* t, const uint32_t* line_slot,
+                                  const forma_affine_range_t* affines, size_t n_affines,
+                                  const forma_stroke_range_t* strokes, size_t n_strokes, size_t* out_points_added) {
+    MULTI_ENTER();
+    ctx->multi->planned = false;
+    EACH_KID(forma_hip_geometry_append_stroked(k, t, line_slot, affines, n_affines, strokes, n_strokes, out_points_added));
+    EACH_KID(fd_set_line_range(k, false, 0, 0));
+    return FORMA_OK;
+}
 int multi_geometry_retain(forma_hip_ctx* ctx, const forma_keep_range_t* keep, size_t n_keep, const uint32_t* slot_remap, size_t n_slots) {
     MULTI_ENTER();
     // (a refused call leaves every device's store as it was: the devices hold the same store and refuse alike, the first one first)

@@ -18,6 +18,14 @@ paths / props built through `forma_amd.api`.  What the reference does, and so wh
   * `style="mix-blend-mode: ..."` -> BlendMode; `fill-rule="evenodd"` -> FillRule.EvenOdd.
   * finally every path is scaled by `scale` (Path::transform, svg.rs:217-220); layer i = path i, Order(i).
 
+`strokes=True` (this loader only; the reference demo has no strokes) draws what the default skips: a `<path>` / `<rect>` with a
+`stroke` yields its fill layer as if it had none (no layer for fill="none") and, right above it, one FillRule.NonZero layer
+with the outline (`api.Path.stroke`): `stroke` (colour), `stroke-width` (default 1), `stroke-linejoin` (miter / round / bevel),
+`stroke-linecap` (butt / round / square), `stroke-miterlimit` (default 4), `stroke-opacity`.  For the outline `Z` closes the
+contour with a real line; the group transform goes onto the control points as for fills and the width is scaled by
+sqrt(|det|) of it and by `scale`.  Dashes (`stroke-dasharray`, `stroke-dashoffset`) are out of scope and ignored: a dashed
+stroke is drawn solid.  A gradient as stroke paint is not supported (opaque black is used).
+
 Two reference quirks are kept because they decide pixels: the arc's x-axis-rotation is passed to cos/sin as written
 (svg.rs:62-63 — degrees treated as radians), and the endpoint's rotated y uses the already rotated x (svg.rs:65-69).
 """
@@ -315,9 +323,11 @@ class Svg:
     """`Svg(path_or_text, scale)` parses; `.paths` = [(api.Path, fill_rule, fill, blend_mode)]; `.compose(composition)`
     inserts layer i at Order(i) like the reference's `App::compose` (svg.rs:895-922)."""
 
-    def __init__(self, source: str, scale: float = 1.0, *, is_text: bool = False):
+    def __init__(self, source: str, scale: float = 1.0, *, is_text: bool = False, strokes: bool = False):
         self.groups: List[_Group] = []
         self.paths: List[Tuple[api.Path, str, tuple, str]] = []
+        self._strokes_on = bool(strokes)
+        self.strokes: Dict[int, api.StrokeStyle] = {}          # index into `paths` -> the style of an outline layer (strokes=True)
         self.gradients: Dict[str, api.Gradient] = {}
         self._gradient: Optional[Tuple[str, api.GradientBuilder]] = None
         self.x = 0.0
@@ -330,6 +340,11 @@ class Svg:
         s = float(scale)
         t9 = [s, 0.0, 0.0, 0.0, s, 0.0, 0.0, 0.0, 1.0]
         self.paths = [(path.transform(t9), fr, fill, bm) for path, fr, fill, bm in self.paths]
+        for i, st in list(self.strokes.items()):               # transform first, then stroke: the width is in scaled units
+            st = api.StrokeStyle(float(f32(st.width) * f32(abs(s))), st.join, st.cap, st.miter_limit)
+            path, fr, fill, bm = self.paths[i]
+            self.strokes[i] = st
+            self.paths[i] = (path.stroke(st), fr, fill, bm)
 
     # -- group state -------------------------------------------------------------------------------------------------
     def _t(self, x, y) -> api.Point:
@@ -368,6 +383,37 @@ class Svg:
     @staticmethod
     def _stroked(attrs) -> bool:
         return attrs.get("stroke", "none") != "none"
+
+    _JOINS = {"miter": api.StrokeJoin.Miter, "round": api.StrokeJoin.Round, "bevel": api.StrokeJoin.Bevel}
+    _CAPS = {"butt": api.StrokeCap.Butt, "round": api.StrokeCap.Round, "square": api.StrokeCap.Square}
+
+    def _stroke_scale(self) -> float:
+        """sqrt(|det|) of the transform `_t` applies: what a width becomes under it"""
+        for g in reversed(self.groups):
+            if g.transform is not None:
+                t = g.transform
+                return math.sqrt(abs(t.a * t.d - t.b * t.c))
+        return 1.0
+
+    def _push_stroke(self, builder: api.PathBuilder, attrs):
+        """the outline layer of a stroked shape: NonZero, the stroke's colour and opacity"""
+        width = _float(attrs.get("stroke-width"))
+        width = 1.0 if width is None else width
+        limit = _float(attrs.get("stroke-miterlimit"))
+        limit = 4.0 if limit is None or limit < 1.0 else limit
+        width = float(f32(width * self._stroke_scale()))
+        if not width > 0.0:
+            return
+        rgb = parse_color(attrs["stroke"]) or (0, 0, 0)
+        op = _float(attrs.get("stroke-opacity"))
+        if op is None:
+            op = _float(attrs.get("opacity"))
+        if op is None:
+            op = self._groups_opacity()
+        c = to_linear(rgb)
+        self.strokes[len(self.paths)] = api.StrokeStyle(width, self._JOINS.get(attrs.get("stroke-linejoin", "miter"), api.StrokeJoin.Miter),
+                                                         self._CAPS.get(attrs.get("stroke-linecap", "butt"), api.StrokeCap.Butt), limit)
+        self.paths.append((builder.build(), api.FillRule.NonZero, api.Fill.Solid(api.Color(c.r, c.g, c.b, op)), _blend_mode(attrs)))
 
     # -- XML events --------------------------------------------------------------------------------------------------
     def _start(self, tag: str, attrs: Dict[str, str]):
@@ -425,16 +471,19 @@ class Svg:
         self.paths.append((builder.build(), rule, self._fill(attrs), _blend_mode(attrs)))
 
     def _rect(self, attrs):
-        if self._stroked(attrs):
+        if self._stroked(attrs) and not self._strokes_on:
             return
         x, y = _float(attrs.get("x")) or 0.0, _float(attrs.get("y")) or 0.0
         w, h = _float(attrs.get("width")), _float(attrs.get("height"))
         if w is None or h is None:
             raise ValueError("rect missing width/height")
         x1, y1 = float(f32(x) + f32(w)), float(f32(y) + f32(h))
-        b = api.PathBuilder()
-        b.move_to(api.Point(x, y)).line_to(api.Point(x, y1)).line_to(api.Point(x1, y1)).line_to(api.Point(x1, y)).line_to(api.Point(x, y))
-        self._push(b, attrs)
+        for outline in ((False, True) if self._stroked(attrs) else (False,)):
+            if not outline and self._stroked(attrs) and attrs.get("fill") == "none":
+                continue
+            b = api.PathBuilder(open_contours=True) if outline else api.PathBuilder()
+            b.move_to(api.Point(x, y)).line_to(api.Point(x, y1)).line_to(api.Point(x1, y1)).line_to(api.Point(x1, y)).line_to(api.Point(x, y))
+            (self._push_stroke if outline else self._push)(b, attrs)
 
     def _arc_to(self, b: api.PathBuilder, arc: _Arc, end):
         """<= quarter-turn rational quadratics, weight cos(sweep/2) (svg.rs:276-335)."""
@@ -460,9 +509,15 @@ class Svg:
         return end
 
     def _path(self, attrs):
-        if self._stroked(attrs) or "d" not in attrs:
+        if "d" not in attrs or (self._stroked(attrs) and not self._strokes_on):
             return
-        b = api.PathBuilder()
+        if not self._stroked(attrs):
+            return self._path_into(api.PathBuilder(), attrs, False)
+        if attrs.get("fill") != "none":
+            self._path_into(api.PathBuilder(), attrs, False)
+        self._path_into(api.PathBuilder(open_contours=True), attrs, True)
+
+    def _path_into(self, b: api.PathBuilder, attrs, outline: bool):
         start = None                                           # first point of the current sub-path, set by the first draw
         end = (f32(0.0), f32(0.0))
         qc = cc = None                                         # last quadratic / cubic control point (for T / S)
@@ -479,6 +534,8 @@ class Svg:
                 continue
             if cmd == "Z":
                 if start is not None:
+                    if outline:
+                        b.close()                              # an outline's closing line is real
                     end, start = start, None
                     qc = cc = None
                 continue
@@ -519,7 +576,7 @@ class Svg:
             if start is None:
                 start = end
             end, qc, cc = p, new_qc, new_cc
-        self._push(b, attrs)
+        (self._push_stroke if outline else self._push)(b, attrs)
 
     # -- App::compose ------------------------------------------------------------------------------------------------
     def compose(self, composition: api.Composition) -> api.Composition:
@@ -530,6 +587,12 @@ class Svg:
                 api.Props(fill_rule=rule, func=api.Func.Draw(api.Style(fill=fill, blend_mode=blend))))
             composition.insert(api.Order(order), layer)
         return composition
+
+
+def load(source: str, scale: float = 1.0, *, is_text: bool = False, strokes: bool = False) -> Svg:
+    """`Svg(source, scale)`.  strokes=False: shapes with a `stroke` are skipped, as the reference demo does; strokes=True: they
+    are drawn, each outline as one FillRule.NonZero layer above the shape's fill (see the module text; dashes are ignored)."""
+    return Svg(source, scale, is_text=is_text, strokes=strokes)
 
 
 def write_svg(shapes, width: int, height: int) -> str:

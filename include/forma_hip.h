@@ -242,6 +242,42 @@ typedef struct forma_keep_range_t   { uint64_t first, count; } forma_keep_range_
  * would reach 2^30 points. */
 int forma_hip_geometry_append(forma_hip_ctx* ctx, const forma_flatten_tables_t* t, const uint32_t* line_slot,
                               const forma_affine_range_t* affines, size_t n_affines);
+/* Stroke paths on the device: forma_hip_geometry_append with a table of STROKE RANGES, ascending disjoint point ranges of `t`
+ * that cover whole contours (a range begins where a contour begins and its last point carries FORMA_NONE).  Points outside every
+ * range go into the store as forma_hip_geometry_append puts them there; the points of a range — after flattening and the affine
+ * of their range — are replaced by the closed polygonal PIECES of their stroke, all wound the same way, so that filling them
+ * with FillRule::NonZero paints the stroke (EvenOdd is wrong for strokes: pieces overlap).  The reference has no strokes.
+ *   contours   closed when its first and last point are bitwise equal, else open.  Lines of zero length emit nothing and a join
+ *              looks through them to the nearest line of non-zero length on each side; a contour without such a line emits nothing.
+ *   body       per line p0 -> p1, d = p1 - p0, len = sqrtf(dx*dx + dy*dy), s = half_width / len, o = (-dy*s, dx*s):
+ *              the quad p0+o, p1+o, p1-o, p0-o.
+ *   join       on the outer side of every interior vertex v, and of the closing vertex of a closed contour.  With oa, ob the
+ *              offsets of the lines that enter and leave v, on a right turn (y up) the pair (us, ue) is (oa, ob), on a left turn
+ *              (-ob, -oa); an exact U-turn counts as a right turn, lines that go on the same way get no join.
+ *              BEVEL v, v+us, v+ue.  MITER v, v+us, v + (us+ue) * hw^2 / (hw^2 + oa.ob), v+ue — a bevel instead where
+ *              1 / cos(theta / 2) exceeds miter_limit.  ROUND a fan from us to ue in equal angular steps, the fewest whose chord's
+ *              sagitta is <= 1/16 px.
+ *   cap        both ends of an open contour: BUTT nothing, SQUARE the body extended by (dx*s, dy*s), ROUND a half fan.
+ *   layout     a piece of k lines is k + 1 points; the last repeats the first and carries FORMA_NONE, the others the slot of the
+ *              source line (a cap: its end's line; a join: the line that leaves the vertex).  Pieces come in source-point order —
+ *              for point i its join or start cap, then the body of line i; the end cap comes with the contour's last point — so
+ *              the store's invariant holds with "flattening and stroking" in place of "flattening".
+ *   arithmetic f32 without contraction, correctly rounded division and sqrtf.
+ * *out_points_added (may be NULL) = points the store grew by.  The call waits for the device twice: once for the total that sizes
+ * the store, once like forma_hip_geometry_append.  n_strokes == 0 is forma_hip_geometry_append.
+ * FORMA_E_ARG, and the store is as it was: everything forma_hip_geometry_append rejects; stroke ranges out of order, overlapping
+ * or beyond t->n_points; a range that does not begin at a contour start or end on a FORMA_NONE; half_width not finite, <= 0 or
+ * above 65536; miter_limit not finite or < 1; an unknown join or cap. */
+#define FORMA_JOIN_BEVEL 0u
+#define FORMA_JOIN_MITER 1u
+#define FORMA_JOIN_ROUND 2u
+#define FORMA_CAP_BUTT   0u
+#define FORMA_CAP_SQUARE 1u
+#define FORMA_CAP_ROUND  2u
+typedef struct forma_stroke_range_t { uint64_t first, count; float half_width, miter_limit; uint32_t join, cap; } forma_stroke_range_t;
+int forma_hip_geometry_append_stroked(forma_hip_ctx* ctx, const forma_flatten_tables_t* t, const uint32_t* line_slot,
+                                      const forma_affine_range_t* affines, size_t n_affines,
+                                      const forma_stroke_range_t* strokes, size_t n_strokes, size_t* out_points_added);
 /* SegmentBuffer::retain (segment.rs:237-273): `keep` lists ascending disjoint point ranges (whole pushes) that survive,
  * order preserved; slot_remap[old slot] = new slot or FORMA_NONE, n_slots entries.  The store is compacted into a second
  * set of buffers which then takes its place (forma_hip_trim releases the spare set).  FORMA_E_ARG — and the store is left

@@ -161,6 +161,24 @@ pub struct forma_keep_range_t {
     pub count: u64,
 }
 
+/// `forma_stroke_range_t`: a point range (whole contours) of an append whose points become the pieces of their stroke.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct forma_stroke_range_t {
+    pub first: u64,
+    pub count: u64,
+    pub half_width: f32,
+    pub miter_limit: f32,
+    pub join: u32,
+    pub cap: u32,
+}
+pub const FORMA_JOIN_BEVEL: u32 = 0;
+pub const FORMA_JOIN_MITER: u32 = 1;
+pub const FORMA_JOIN_ROUND: u32 = 2;
+pub const FORMA_CAP_BUTT: u32 = 0;
+pub const FORMA_CAP_SQUARE: u32 = 1;
+pub const FORMA_CAP_ROUND: u32 = 2;
+
 /// `forma_counters_t`: monotonic counters since `forma_hip_create` (what the geometry edits cost, how the frames ran).
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -266,6 +284,16 @@ extern "C" {
         line_slot: *const u32,
         affines: *const forma_affine_range_t,
         n_affines: usize,
+    ) -> c_int;
+    pub fn forma_hip_geometry_append_stroked(
+        ctx: *mut forma_hip_ctx,
+        t: *const forma_flatten_tables_t,
+        line_slot: *const u32,
+        affines: *const forma_affine_range_t,
+        n_affines: usize,
+        strokes: *const forma_stroke_range_t,
+        n_strokes: usize,
+        out_points_added: *mut usize,
     ) -> c_int;
     pub fn forma_hip_geometry_retain(
         ctx: *mut forma_hip_ctx,

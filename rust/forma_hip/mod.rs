@@ -931,3 +931,22 @@ pub fn flatten_on_device(t: &FlattenTables<'_>) -> Option<(Vec<f32>, Vec<f32>)> 
     (rc == 0).then_some((x, y))
 }
 
+/// Thin wrapper of `forma_hip_geometry_append_stroked`: flatten `tables` into the tail of `ctx`'s geometry store and replace
+/// the points of every stroke range (whole contours) by the closed pieces of their stroke — fill them with `FillRule::NonZero`.
+/// Returns the number of points the store grew by, or the library's error code.
+///
+/// # Safety
+/// `ctx` is a live context; `tables` borrows arrays that outlive the call; `line_slot` has `tables.n_points` entries.
+pub unsafe fn geometry_append_stroked(
+    ctx: *mut ffi::forma_hip_ctx,
+    tables: &ffi::forma_flatten_tables_t,
+    line_slot: &[u32],
+    affines: &[ffi::forma_affine_range_t],
+    strokes: &[ffi::forma_stroke_range_t],
+) -> Result<usize, i32> {
+    let mut added = 0usize;
+    let rc = ffi::forma_hip_geometry_append_stroked(
+        ctx, tables, line_slot.as_ptr(), affines.as_ptr(), affines.len(), strokes.as_ptr(), strokes.len(), &mut added,
+    );
+    if rc == ffi::FORMA_OK { Ok(added) } else { Err(rc) }
+}
